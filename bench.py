@@ -6,7 +6,7 @@ One step = zero_grad -> forward (models/model.py:53-73) -> BCEWithLogits + Dice
 synthetic bs=32 x 1x256x256 batch per GPU (BASELINE config 2; config 3 = 8 ranks x 32),
 inputs resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         N > 1 without a launcher: this process starts N rank processes of itself (one per
         GPU, RCCL over xGMI; rank env + 127.0.0.1 rendezvous) and exits with their status
     torchrun --nproc-per-node N bench.py --gpus N ...   (same ranks, started by torchrun)
@@ -15,14 +15,26 @@ inputs resident in HBM before the timed region.
                                     (BASELINE config 4; not the headline metric)
 
 Prints ONE JSON line on rank 0.  ``value`` = images/s of the whole job (sum over ranks,
-time = max over ranks).  ``roofline`` is for the dominant kernel (most GPU time in one extra untimed
-profiling step), from per-launch HIP events recorded on the launch stream inside the
-library around that kernel's launches in the timed region: achieved = algorithmic FLOP
-of its launches / their summed duration.
-``step_ms_median`` / ``step_ms_p90`` are per-step device times (HIP events at the step
-boundaries on the launch stream).  ``cpu_baseline`` times the CPU oracle
+time = max over ranks) over the K timed steps, ``ms_per_step`` = the wall time of one timed
+step.  ``step_ms_median`` / ``step_ms_p90`` are per-step device times (HIP events at the step
+boundaries on the launch stream).  A plain run does nothing else: set up, W warm-up steps,
+K timed steps, the result line.
+
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0) as DIR/<name>.npy:
+``loss`` ([total, bce, dice], float64), ``logits`` (float32, the whole batch), ``bn_stats``
+(the BatchNorm running statistics, float32) and fixed seeded samples of the updated
+parameters and of their gradients (``param_sample`` / ``grad_sample`` at flat-arena indices
+``sample_index``).  Inputs and initial weights are seeded, so two builds run with the same
+arguments can be compared output for output.
+
+``--full`` adds what takes runs of its own.  ``roofline`` is for the dominant kernel (most
+GPU time in one extra untimed profiling step), from per-launch HIP events recorded on the
+launch stream inside the library around that kernel's launches in the timed region:
+achieved = algorithmic FLOP of its launches / their summed duration (``--verbose`` prints
+the profiling step's per-kernel breakdown).  ``cpu_baseline`` times the CPU oracle
 (oracle/unet_ref_cpu.py, a torch-CPU restatement of the reference's step) on a bounded
-sample (bs=4, median of 3 steps) on rank 0 only -- the only use of oracle/ here.
+sample (bs=4, median of 3 steps) on rank 0 only, and ``dice_vs_ref`` compares the HIP
+path's first step with it -- the only use of oracle/ here.
 """
 import argparse
 import json
@@ -61,9 +73,16 @@ def parse():
                     "reference grid's narrow ResUNet; default 64 = main.py's ResUNet())")
     ap.add_argument("--depth", type=int, default=5, help="config res: depth")
     ap.add_argument("--size", type=int, default=0, help="image side (default 256 / 512)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the profiling step and the dominant kernel's roofline, the CPU "
+                         "baseline and dice_vs_ref (off by default: a plain run only times "
+                         "the steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle")
     ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--verbose", action="store_true",
+                    help="--full: per-kernel / per-layer breakdown of the profiling step on stderr")
     ap.add_argument("--adamw", default="fused", choices=("fused", "plain"),
                     help="fused: AdamW with the next forward's weight repack (unet_adamw_repack, "
                          "the default); plain: unet_adamw + the forward's repack (A/B runs)")
@@ -76,7 +95,12 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher plumbing check: every rank prints its rank environment as "
                          "one JSON line and exits (no torch, no GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.verbose and not args.full:
+        ap.error("--verbose prints the breakdown of --full's profiling step: add --full")
+    return args
 
 
 _RANK_ENV = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")
@@ -270,6 +294,34 @@ def dice_vs_ref(sample, dev):
             "logits_max_rel": float(f"{float((lg - ref['logits']).abs().max() / ref['logits'].abs().max()):.3g}")}
 
 
+DUMP_SAMPLE = 1 << 20  # parameters / gradients sampled by --dump-outputs (4 MiB each)
+
+
+def dump_outputs(path, model, loss, logits, losses):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy --
+    the losses, the logits, the BatchNorm running statistics, and the updated parameters and
+    their gradients at DUMP_SAMPLE fixed (seeded) indices of the flat arenas (config 4 has
+    497 M parameters; everything written stays far below 64 MB).  Returns the file names."""
+    import numpy as np
+    import torch
+    st = model.flatten_()
+    n = st.param_arena.numel()
+    idx = torch.from_numpy(np.sort(np.random.default_rng(12345).integers(0, n, DUMP_SAMPLE)))
+    didx = idx.to(st.param_arena.device)
+    arrays = {
+        "loss": np.array([loss.item(), losses[0].item(), losses[1].item()], dtype=np.float64),
+        "logits": logits.detach().float().cpu().numpy(),
+        "bn_stats": st.bn_arena.detach().float().cpu().numpy(),
+        "sample_index": idx.numpy().astype(np.float64),
+        "param_sample": st.param_arena.detach()[didx].float().cpu().numpy(),
+        "grad_sample": st.grad_arena.detach()[didx].float().cpu().numpy(),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(name + ".npy" for name in arrays)
+
+
 def load_pmc(kernel, config=2, mfma="fp32"):
     """HBM bytes per launch of `kernel` from the committed rocprofv3 PMC summary of this
     workload (profiles/pmc_summary.json: config 2; pmc_summary_c4_<mfma>.json), if any."""
@@ -366,7 +418,7 @@ def main():
         if ddp is not None:
             ddp.reduce_gradients()
         opt.step()
-        return loss
+        return loss, logits, losses
 
     for _ in range(args.warmup):
         step()
@@ -389,19 +441,20 @@ def main():
                 e[2] += flop
         return fam, kern, layer
 
-    # 1. one untimed profiling step with an event pair around every launch: the per-kernel
-    #    breakdown and which kernel instance dominates the GPU time
-    rt.timing(True)
-    step()
-    torch.cuda.synchronize()
-    fam, kern, layer = aggregate(rt.timing_records())
-    rt.timing(False)
-    # the dominant MFMA kernel: most GPU time among the kernel instances with algorithmic
-    # FLOPs (GEMMs; bandwidth passes carry none and have no MFMA roofline)
-    dom = max((k for k in kern if kern[k][2] > 0), key=lambda k: kern[k][1])
-    # 2. the timed region: events only around the dominant kernel's launches (so the
-    #    per-launch markers of ~400 other launches do not inflate the step time)
-    rt.timing(True, only=None if args.timing == "all" else f"/{dom}|")
+    if args.full:
+        # 1. one untimed profiling step with an event pair around every launch: the per-kernel
+        #    breakdown and which kernel instance dominates the GPU time
+        rt.timing(True)
+        step()
+        torch.cuda.synchronize()
+        fam, kern, layer = aggregate(rt.timing_records())
+        rt.timing(False)
+        # the dominant MFMA kernel: most GPU time among the kernel instances with algorithmic
+        # FLOPs (GEMMs; bandwidth passes carry none and have no MFMA roofline)
+        dom = max((k for k in kern if kern[k][2] > 0), key=lambda k: kern[k][1])
+        # 2. the timed region: events only around the dominant kernel's launches (so the
+        #    per-launch markers of ~400 other launches do not inflate the step time)
+        rt.timing(True, only=None if args.timing == "all" else f"/{dom}|")
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -411,14 +464,15 @@ def main():
     t0 = time.perf_counter()
     evs[0].record()
     for i in range(args.steps):
-        loss = step()
+        loss, logits, losses = step()
         evs[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    recs = rt.timing_records()
-    rt.timing(False)
+    if args.full:
+        recs = rt.timing_records()
+        rt.timing(False)
     if world > 1:
         te = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
@@ -432,52 +486,53 @@ def main():
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
     step_med = step_ms[len(step_ms) // 2]
     step_p90 = step_ms[min(len(step_ms) - 1, int(0.9 * len(step_ms)))]
-    _, kern_t, _ = aggregate(recs)
-    prof_steps = 1
-    n_l, t_l, f_l = kern_t[dom]
-    achieved = f_l / (t_l * 1e-3) / 1e12 if t_l > 0 else 0.0
-    per_launch_flop = f_l / n_l
-    pmc = load_pmc(dom, args.config, args.mfma)
-    conv_flop = (train_flops_per_image(S, S, 128, 5) if c4 else
-                 res_train_flops_per_image(S, S, args.base, args.depth) if cres else
-                 train_flops_per_image(S, S)) * B
     bf16 = c4 and args.mfma == "bf16"
+    if args.full:
+        _, kern_t, _ = aggregate(recs)
+        prof_steps = 1
+        n_l, t_l, f_l = kern_t[dom]
+        achieved = f_l / (t_l * 1e-3) / 1e12 if t_l > 0 else 0.0
+        per_launch_flop = f_l / n_l
+        pmc = load_pmc(dom, args.config, args.mfma)
+        conv_flop = (train_flops_per_image(S, S, 128, 5) if c4 else
+                     res_train_flops_per_image(S, S, args.base, args.depth) if cres else
+                     train_flops_per_image(S, S)) * B
 
-    def kpeak(k):
-        """MFMA peak of one kernel instance's arithmetic: x3 kernels (exact 3-way splits on
-        the bf16 matrix cores) bf16 / 6; the bf16 network's GEMMs bf16; the rest f32 MFMA."""
-        if k.startswith("x3") or k.startswith("wx3"):
-            return X3_MFMA_PEAK_TFLOPS
-        return BF16_MFMA_PEAK_TFLOPS if bf16 else FP32_MFMA_PEAK_TFLOPS
-    x3 = kpeak(dom) == X3_MFMA_PEAK_TFLOPS
-    peak = kpeak(dom)
-    # the step's conv work runs on several kernel families with different peaks (ResUNet's
-    # 32-channel levels and 1x1 skips stay on f32 MFMA beside the x3 GEMMs): price the step
-    # against the FLOP-weighted peak of the families that ran it (profiling step's FLOPs)
-    fam_flop = {}
-    for k, (_, _, fl) in kern.items():
-        if fl > 0:
-            fam_flop[kpeak(k)] = fam_flop.get(kpeak(k), 0.0) + fl
-    tot_flop = sum(fam_flop.values())
-    step_peak = tot_flop / sum(fl / pk for pk, fl in fam_flop.items()) if tot_flop else peak
-    names = {X3_MFMA_PEAK_TFLOPS: "x3", BF16_MFMA_PEAK_TFLOPS: "bf16", FP32_MFMA_PEAK_TFLOPS: "f32_mfma"}
-    peak_mix = {names[pk]: round(fl / tot_flop, 4) for pk, fl in sorted(fam_flop.items())} if tot_flop else {}
-    roofline = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 3),
-                "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4),
-                "traffic": pmc, "launches": n_l, "avg_launch_ms": round(t_l / n_l, 4),
-                "flop_per_launch": per_launch_flop,
-                "kernel_share_of_gpu_time": round(kern[dom][1] / max(1e-9, sum(v[1] for v in kern.values())), 4),
-                "step_conv_tflops": round(conv_flop / (ms * 1e-3) / 1e12, 3),
-                "step_conv_frac": round(conv_flop / (ms * 1e-3) / 1e12 / step_peak, 4),
-                "step_peak_tflops": round(step_peak, 2),
-                "step_flop_share_by_arith": peak_mix}
-    if x3:
-        roofline["peak_note"] = ("f32 GEMM on bf16 MFMA through exact 3-way operand splits: 6 bf16 "
-                                 "products per f32 product, so the peak is the bf16 dense peak / 6")
-        roofline["fp32_mfma_peak_frac"] = round(achieved / FP32_MFMA_PEAK_TFLOPS, 4)
-        roofline["step_conv_fp32_mfma_frac"] = round(conv_flop / (ms * 1e-3) / 1e12 /
-                                                     FP32_MFMA_PEAK_TFLOPS, 4)
+        def kpeak(k):
+            """MFMA peak of one kernel instance's arithmetic: x3 kernels (exact 3-way splits on
+            the bf16 matrix cores) bf16 / 6; the bf16 network's GEMMs bf16; the rest f32 MFMA."""
+            if k.startswith("x3") or k.startswith("wx3"):
+                return X3_MFMA_PEAK_TFLOPS
+            return BF16_MFMA_PEAK_TFLOPS if bf16 else FP32_MFMA_PEAK_TFLOPS
+        x3 = kpeak(dom) == X3_MFMA_PEAK_TFLOPS
+        peak = kpeak(dom)
+        # the step's conv work runs on several kernel families with different peaks (ResUNet's
+        # 32-channel levels and 1x1 skips stay on f32 MFMA beside the x3 GEMMs): price the step
+        # against the FLOP-weighted peak of the families that ran it (profiling step's FLOPs)
+        fam_flop = {}
+        for k, (_, _, fl) in kern.items():
+            if fl > 0:
+                fam_flop[kpeak(k)] = fam_flop.get(kpeak(k), 0.0) + fl
+        tot_flop = sum(fam_flop.values())
+        step_peak = tot_flop / sum(fl / pk for pk, fl in fam_flop.items()) if tot_flop else peak
+        names = {X3_MFMA_PEAK_TFLOPS: "x3", BF16_MFMA_PEAK_TFLOPS: "bf16", FP32_MFMA_PEAK_TFLOPS: "f32_mfma"}
+        peak_mix = {names[pk]: round(fl / tot_flop, 4) for pk, fl in sorted(fam_flop.items())} if tot_flop else {}
+        roofline = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 3),
+                    "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(achieved / peak, 4),
+                    "traffic": pmc, "launches": n_l, "avg_launch_ms": round(t_l / n_l, 4),
+                    "flop_per_launch": per_launch_flop,
+                    "kernel_share_of_gpu_time": round(kern[dom][1] / max(1e-9, sum(v[1] for v in kern.values())), 4),
+                    "step_conv_tflops": round(conv_flop / (ms * 1e-3) / 1e12, 3),
+                    "step_conv_frac": round(conv_flop / (ms * 1e-3) / 1e12 / step_peak, 4),
+                    "step_peak_tflops": round(step_peak, 2),
+                    "step_flop_share_by_arith": peak_mix}
+        if x3:
+            roofline["peak_note"] = ("f32 GEMM on bf16 MFMA through exact 3-way operand splits: 6 bf16 "
+                                     "products per f32 product, so the peak is the bf16 dense peak / 6")
+            roofline["fp32_mfma_peak_frac"] = round(achieved / FP32_MFMA_PEAK_TFLOPS, 4)
+            roofline["step_conv_fp32_mfma_frac"] = round(conv_flop / (ms * 1e-3) / 1e12 /
+                                                         FP32_MFMA_PEAK_TFLOPS, 4)
 
     if cres:
         metric = f"images/sec fwd+bwd, mod.ResUNet(base {args.base}, depth {args.depth}) {S}x{S}x1 bs={B}/GPU"
@@ -520,15 +575,18 @@ def main():
            "config": {"workload": workload, "model": mname, "global_batch": B * world,
                       "image": [1, S, S], "parallelism": f"dp{world}"},
            "ranks": dist.get_world_size() if world > 1 else 1,
-           "backend": (("rccl" if backend == "nccl" else backend) if world > 1 else None),
-           "roofline": roofline}
+           "backend": (("rccl" if backend == "nccl" else backend) if world > 1 else None)}
     assert out["n_gpus"] == out["ranks"], (out["n_gpus"], out["ranks"])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not cres:
-        sample, out["cpu_baseline"] = cpu_baseline(args.cpu_steps, S, int(args.config))
-        if sample is not None:
-            out["dice_vs_ref"] = dice_vs_ref(sample, dev)
-    elif rank == 0:
-        out["cpu_baseline"] = None
+    if rank == 0 and args.dump_outputs:
+        out["outputs"] = dump_outputs(args.dump_outputs, model, loss, logits, losses)
+    if args.full:
+        out["roofline"] = roofline
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and not cres:
+            sample, out["cpu_baseline"] = cpu_baseline(args.cpu_steps, S, int(args.config))
+            if sample is not None:
+                out["dice_vs_ref"] = dice_vs_ref(sample, dev)
+        elif rank == 0:
+            out["cpu_baseline"] = None
     if rank == 0:
         if args.verbose:
             for k, (n, tm, fl) in sorted(fam.items(), key=lambda kv: -kv[1][1]):

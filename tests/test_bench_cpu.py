@@ -96,3 +96,17 @@ def test_launcher_forwards_sigterm_to_ranks():
         except ProcessLookupError:
             alive = False
         assert not alive, pid
+
+
+def test_verbose_breakdown_needs_full():
+    """--verbose prints the per-kernel breakdown of --full's profiling step; a plain run has
+    no such step, so the combination is refused instead of silently printing nothing."""
+    r = _run(["--gpus", "1", "--verbose", "--dry-run"])
+    assert r.returncode == 2 and "--full" in r.stderr
+    r = _run(["--gpus", "1", "--full", "--verbose", "--dump-outputs", "unused", "--dry-run"])
+    assert r.returncode == 0, r.stderr
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0", "--dry-run"])
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -128,24 +128,31 @@ def test_state_dict_keys_match_reference():
     assert bufs == want
 
 
-def test_init_consumes_rng_like_reference():
-    """Same seed -> same initial weights as models/model.py:UNet (checked against the
-    reference module only where it is importable, i.e. in the build container)."""
+def _tensor_digest(t):
+    """SHA-256 of a tensor's dtype, shape and bytes (as tools/gen_golden.py records it)."""
+    import hashlib
+    a = np.ascontiguousarray(t.detach().cpu().numpy())
+    return hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).hexdigest()
+
+
+def _assert_init_like_reference(key, make):
+    """make() after torch.manual_seed(42) has the reference module's state_dict bit for bit:
+    tests/golden/init_seed42.json holds the names, shapes and per-tensor SHA-256 of the
+    reference's own modules built after the same seed (tools/gen_golden.py init_seed42)."""
+    import json
     import torch
+    want = json.load(open(os.path.join(REPO, "tests", "golden", "init_seed42.json")))[key]
+    torch.manual_seed(42)
+    got = make().state_dict()
+    assert list(got) == [w[0] for w in want]
+    for (name, shape, digest), (nb, pb) in zip(want, got.items()):
+        assert list(pb.shape) == shape and _tensor_digest(pb) == digest, name
+
+
+def test_init_consumes_rng_like_reference():
+    """Same seed -> same initial weights as models/model.py:UNet."""
     import unet_hip
-    ref_dir = "/root/reference"
-    if not os.path.isdir(ref_dir):
-        pytest.skip("reference not present (GPU box)")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_ref_model", os.path.join(ref_dir, "models", "model.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    torch.manual_seed(42)
-    a = mod.UNet(1, 1)
-    torch.manual_seed(42)
-    b = unet_hip.UNet(1, 1)
-    for (na, pa), (nb, pb) in zip(a.state_dict().items(), b.state_dict().items()):
-        assert na == nb and torch.equal(pa, pb), na
+    _assert_init_like_reference("unet", lambda: unet_hip.UNet(1, 1))
 
 
 # ---------------------------------------------------------------- models/mod.py:UNet
@@ -218,19 +225,7 @@ def test_mod_state_dict_and_rng_like_reference():
     for n, _ in MO.bn_layers(64, 3):
         want += [f"{n}.running_mean", f"{n}.running_var", f"{n}.num_batches_tracked"]
     assert [n for n, _ in m.named_buffers()] == want
-    ref_dir = "/root/reference"
-    if not os.path.isdir(ref_dir):
-        pytest.skip("reference not present (GPU box)")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_ref_mod", os.path.join(ref_dir, "models", "mod.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    torch.manual_seed(42)
-    a = mod.UNet(1, 1, base_filters=64, depth=3)
-    torch.manual_seed(42)
-    b = unet_hip.ModUNet(1, 1, base_filters=64, depth=3)
-    for (na, pa), (nb, pb) in zip(a.state_dict().items(), b.state_dict().items()):
-        assert na == nb and torch.equal(pa, pb), na
+    _assert_init_like_reference("mod_64_3", lambda: unet_hip.ModUNet(1, 1, base_filters=64, depth=3))
 
 
 def test_bf16_math_only_for_mod_variant():
@@ -276,19 +271,7 @@ def test_res_tables_and_rng_like_reference():
     m = unet_hip.ResUNet(1, 1, base_filters=64, depth=3)
     assert [n for n, _ in m.named_parameters()] == [s[0] for s in spec]
     assert rt.workspace_bytes(2, 64, 64, True) > 0
-    ref_dir = "/root/reference"
-    if not os.path.isdir(ref_dir):
-        pytest.skip("reference not present (GPU box)")
-    import importlib.util
-    sp = importlib.util.spec_from_file_location("_ref_mod2", os.path.join(ref_dir, "models", "mod.py"))
-    mod = importlib.util.module_from_spec(sp)
-    sp.loader.exec_module(mod)
-    torch.manual_seed(42)
-    a = mod.ResUNet(1, 1, base_filters=64, depth=3)
-    torch.manual_seed(42)
-    b = unet_hip.ResUNet(1, 1, base_filters=64, depth=3)
-    for (na, pa), (nb, pb) in zip(a.state_dict().items(), b.state_dict().items()):
-        assert na == nb and torch.equal(pa, pb), na
+    _assert_init_like_reference("res_64_3", lambda: unet_hip.ResUNet(1, 1, base_filters=64, depth=3))
 
 
 def test_schedule_options_are_explicit(rt, monkeypatch):

@@ -59,6 +59,11 @@ Fixtures (all float64 statistics computed from fp32 results):
                     over two replicas (shards 2 + 1), BCE + Dice of the gathered logits, two
                     AdamW steps (lr 1e-4): logits, losses, grad norm/sum/samples, param
                     samples, running stats per step; eval logits with replica 0's buffers.
+  init_seed42.json  the reference modules' own initialisation after torch.manual_seed(42):
+                    state_dict names, shapes and the SHA-256 of every tensor's bytes for
+                    model.py UNet(1, 1) (unet), mod.py UNet(1, 1, 64, 3) (mod_64_3) and mod.py
+                    ResUNet(1, 1, 64, 3) (res_64_3) -- pins that the HIP modules consume the
+                    RNG like the reference without the reference at test time.
 """
 import os
 import sys
@@ -522,6 +527,27 @@ def case_mod_c4_64():
     np.savez_compressed(os.path.join(OUT, "mod_c4_64.npz"), **out)
 
 
+def tensor_digest(t):
+    """SHA-256 of a tensor's dtype, shape and bytes (tests/_helpers.py restates it)."""
+    import hashlib
+    a = np.ascontiguousarray(t.detach().cpu().numpy())
+    return hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).hexdigest()
+
+
+def case_init_seed42():
+    import json
+    out = {}
+    for key, make in (("unet", lambda: RefUNet(1, 1)),
+                      ("mod_64_3", lambda: RefModUNet(1, 1, base_filters=64, depth=3)),
+                      ("res_64_3", lambda: RefResUNet(1, 1, base_filters=64, depth=3))):
+        torch.manual_seed(42)
+        sd = make().state_dict()
+        out[key] = [[n, list(v.shape), tensor_digest(v)] for n, v in sd.items()]
+    with open(os.path.join(OUT, "init_seed42.json"), "w") as f:
+        models = [f'"{k}": [\n' + ",\n".join(json.dumps(e) for e in v) + "\n]" for k, v in out.items()]
+        f.write("{\n" + ",\n".join(models) + "\n}\n")  # one tensor per line
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     os.makedirs(OUT, exist_ok=True)
@@ -542,5 +568,6 @@ if __name__ == "__main__":
     case_mod_narrow_64()
     case_dp_eval_64()
     case_dp_modres_64()
+    case_init_seed42()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -4,8 +4,8 @@
 #   usage: bash tools/gpu_r06b.sh TAG ROUNDS "SET1" "SET2" ...
 set -u
 cd $GRAFT_REPO_ROOT
+OUT=${OUT:-bench_out}; mkdir -p $OUT  # where this script writes its results
 TAG=$1; N=$2; shift 2
-mkdir -p gpurun_out
 bash tools/gpu_suite.sh $TAG
 rc=$?
 [ $rc -ne 0 ] && [ $rc -ne 1 ] && exit $rc

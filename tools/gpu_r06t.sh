@@ -3,14 +3,14 @@
 #   usage: bash tools/gpu_r06t.sh TAG "PYTEST_K" ROUNDS "SET1" "SET2" ...   (SET: a,b=c or "-")
 set -u
 cd $GRAFT_REPO_ROOT
+OUT=${OUT:-bench_out}; mkdir -p $OUT  # where this script writes its results
 TAG=$1; K=$2; N=$3; shift 3
-mkdir -p gpurun_out
 if [ "$K" != "-" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout-method thread \
-    -p no:cacheprovider -k "$K" > gpurun_out/$TAG.pytest.log 2>&1
+    -p no:cacheprovider -k "$K" > $OUT/$TAG.pytest.log 2>&1
   rc=$?
-  echo "pytest rc=$rc"; grep -E "passed|failed|error" gpurun_out/$TAG.pytest.log | tail -2
-  grep -E "^FAILED|^ERROR|Error" gpurun_out/$TAG.pytest.log | head -20
+  echo "pytest rc=$rc"; grep -E "passed|failed|error" $OUT/$TAG.pytest.log | tail -2
+  grep -E "^FAILED|^ERROR|Error" $OUT/$TAG.pytest.log | head -20
   [ $rc -ne 0 ] && exit $rc
 fi
 [ "$N" = "0" ] && exit 0
