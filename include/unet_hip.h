@@ -22,6 +22,10 @@
  *                                                           FocalTverskyLoss (two phases so DP
  *                                                           can all-reduce the batch sums)
  *   unet_loss_bwd                   utils/trainer.py:90-91 d(weighted loss)/d(logits)
+ *   unet_edt / unet_edt_host        models/loss.py:55-61   targets.astype(uint8) and scipy's
+ *                                                           distance_transform_edt(1 - gt), on the
+ *                                                           device (no host round trip)
+ *   unet_boundary_fwd / _bwd        models/loss.py:52-66   BoundaryLoss and its d/d(logits)
  *   unet_adamw                      utils/trainer.py:41,92 AdamW.step (torch optim/adam.py
  *                                                           _single_tensor_adam, decoupled wd)
  *   unet_mask_counts                utils/trainer.py:217,236-242  sigmoid(x)>0.5 masks and
@@ -164,6 +168,36 @@ int unet_loss_fwd(unet_ctx* ctx, const float* logits, const float* targets, int 
 int unet_loss_bwd(unet_ctx* ctx, const float* logits, const float* targets, int N, int C, int H,
                   int W, const float* stats, const double* sums, const float* w, float* dlogits,
                   float focal_alpha, float focal_beta, float focal_gamma, unet_stream_t stream);
+
+/* BoundaryLoss (models/loss.py:48-66): mean_n mean_hw |sigmoid(x[n,0]) - t[n,0]| * dist[n], dist
+ * the exact Euclidean distance transform of the target (models/loss.py:55-61:
+ * scipy.ndimage.distance_transform_edt(1 - targets.astype(np.uint8)[n, 0])).
+ *   unet_edt       targets (N, C, H, W) f32, only channel 0 read -> dist (N, 1, H, W) f32, bit for
+ *                  bit scipy's float64 result cast to float32.  A pixel is a feature site
+ *                  (distance 0) iff (uint8)t == 1, i.e. 1 <= t < 2: a soft mixup target below 1 is
+ *                  not a site.  dist = sqrt(min over sites of dy^2 + dx^2), the minimum exact in
+ *                  int32.  A sample WITHOUT any site gets scipy's answer for an all-background
+ *                  input, the distance to a virtual site at row -1, column 0:
+ *                  sqrt((i + 1)^2 + j^2) (observed with scipy 1.15; the reference trains on it).
+ *                  max(H, W) > 2048 is UNET_ERR_SHAPE (keeps the squared distance below 2^24,
+ *                  where the float32 result is exact); no other shape constraint.
+ *   unet_edt_host  HOST function: the same 1-D passes (csrc/edt.h, shared host / device source)
+ *                  on host pointers.
+ *   unet_boundary_fwd  sum (device fp64[1]) = sum_n mean_hw |p - t| dist (per sample in chunks,
+ *                  then double, as unet_loss_stats), loss (device fp32[1]) = sum / N.
+ *   unet_boundary_bwd  dlogits[n,0] = w[0] sign(p - t) dist p (1 - p) / (N H W) with sign(0) = 0
+ *                  (torch's abs backward), w a device fp32[1]; channels 1.. are written as zero.
+ * All work is enqueued on `stream` with no host synchronisation; the scratch is owned by the
+ * context and grown on demand (an outgrown buffer is released by unet_destroy), so issue a
+ * context's boundary calls on one stream, or order the streams. */
+int unet_edt(unet_ctx* ctx, const float* targets, int N, int C, int H, int W, float* dist,
+             unet_stream_t stream);
+int unet_edt_host(const float* targets, int N, int C, int H, int W, float* dist);
+int unet_boundary_fwd(unet_ctx* ctx, const float* logits, const float* targets, const float* dist,
+                      int N, int C, int H, int W, double* sum, float* loss, unet_stream_t stream);
+int unet_boundary_bwd(unet_ctx* ctx, const float* logits, const float* targets, const float* dist,
+                      int N, int C, int H, int W, const float* w, float* dlogits,
+                      unet_stream_t stream);
 
 /* AdamW over flat arenas of n floats (one launch for all parameter tensors).
  * Hyper-parameters are the optimizer's Python floats (double); the library forms

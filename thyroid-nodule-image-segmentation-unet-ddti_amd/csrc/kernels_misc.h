@@ -121,6 +121,15 @@ int k_loss_finalize(const double* sums, float alpha, float beta, float gamma, fl
 int k_loss_bwd(const float* x, const float* t, int N, int64_t per, const float* stats,
                const double* sums, const float* w, float alpha, float beta, float gamma, float* dx,
                hipStream_t s);
+// BoundaryLoss (kernels_edt.hip; algorithm and rules in edt.h).  scratch holds
+// edt_scratch_ints(N, H, W) ints; part holds N * loss_groups(hw) floats, hw = H * W
+int64_t edt_scratch_ints(int N, int H, int W);
+int k_edt(const float* t, int N, int C, int H, int W, int* scratch, float* dist, hipStream_t s);
+void edt_host(const float* t, int N, int C, int H, int W, int* g2, float* dist);
+int k_boundary_fwd(const float* x, const float* t, const float* dist, int N, int C, int64_t hw,
+                   float* part, double* sum, float* loss, hipStream_t s);
+int k_boundary_bwd(const float* x, const float* t, const float* dist, int N, int C, int64_t hw,
+                   const float* w, float* dx, hipStream_t s);
 // AdamW scalars, each formed in double and rounded to float once (torch Scalar -> float)
 struct AdamwScalars {
     float decay;     // 1 - lr * weight_decay

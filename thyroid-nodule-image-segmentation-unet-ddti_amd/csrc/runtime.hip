@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/unet_hip.h"
+#include "edt.h"
 #include "kernels_misc.h"
 #include "x3_split.h"
 
@@ -286,6 +287,12 @@ struct unet_ctx {
     // (r06) per-chunk loss statistics of unet_loss_stats (4 floats per chunk, grown on demand)
     float* lpart = nullptr;
     int64_t lpart_n = 0;
+    // BoundaryLoss scratch (unet_edt: any-site flags + g^2; unet_boundary_fwd: chunk sums),
+    // grown on demand without a host synchronisation: an outgrown buffer may still be read by
+    // work in flight, so it is kept until unet_destroy
+    void* bscr = nullptr;
+    size_t bscr_bytes = 0;
+    std::vector<void*> bscr_old;
     const float* pp_src = nullptr;
     bool pp_ok = false;
     uint64_t pp_gen = 0;
@@ -2409,11 +2416,13 @@ int unet_destroy(unet_ctx* c) {
     if (!c) return UNET_ERR_INVALID;
     for (auto e : c->bucket_ev) (void)hipEventDestroy(e);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->pp || c->pp3 || c->lpart) {
+    if (c->pp || c->pp3 || c->lpart || c->bscr) {
         (void)hipSetDevice(c->device);
         if (c->pp) (void)hipFree(c->pp);
         if (c->pp3) (void)hipFree(c->pp3);
         if (c->lpart) (void)hipFree(c->lpart);
+        if (c->bscr) (void)hipFree(c->bscr);
+        for (void* p : c->bscr_old) (void)hipFree(p);
     }
     delete c;
     return UNET_OK;
@@ -2598,6 +2607,76 @@ int unet_loss_bwd(unet_ctx* c, const float* logits, const float* targets, int N,
     int r = k_loss_bwd(logits, targets, N, (int64_t)C * H * W, stats, sums, w, fa, fb, fg, dlogits,
                        (hipStream_t)stream);
     return r ? fail(c, UNET_ERR_HIP, "loss_bwd launch %d", r) : UNET_OK;
+    ABI_CATCH(c)
+}
+
+// BoundaryLoss scratch of at least `bytes`; never synchronises (see unet_ctx::bscr)
+static int boundary_scratch(unet_ctx* c, size_t bytes) {
+    if (bytes <= c->bscr_bytes) return UNET_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, UNET_ERR_HIP, "hipSetDevice");
+    if (c->bscr) c->bscr_old.reserve(c->bscr_old.size() + 1);
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess)
+        return fail(c, UNET_ERR_HIP, "hipMalloc: boundary scratch: %zu bytes", bytes);
+    if (c->bscr) c->bscr_old.push_back(c->bscr);
+    c->bscr = p;
+    c->bscr_bytes = bytes;
+    return UNET_OK;
+}
+
+static bool edt_shape_ok(int N, int C, int H, int W) {
+    return N >= 1 && C >= 1 && H >= 1 && W >= 1 && H <= EDT_MAX_SIDE && W <= EDT_MAX_SIDE &&
+           (int64_t)N * std::max(H, W) < (int64_t)1 << 31;
+}
+
+int unet_edt(unet_ctx* c, const float* targets, int N, int C, int H, int W, float* dist,
+             unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !targets || !dist) return UNET_ERR_INVALID;
+    if (!edt_shape_ok(N, C, H, W))
+        return fail(c, UNET_ERR_SHAPE, "edt: N, C, H, W >= 1 and max(H, W) <= %d", EDT_MAX_SIDE);
+    if (int r = boundary_scratch(c, sizeof(int) * (size_t)edt_scratch_ints(N, H, W))) return r;
+    int r = k_edt(targets, N, C, H, W, (int*)c->bscr, dist, (hipStream_t)stream);
+    return r ? fail(c, UNET_ERR_HIP, "edt launch %d", r) : UNET_OK;
+    ABI_CATCH(c)
+}
+
+int unet_edt_host(const float* targets, int N, int C, int H, int W, float* dist) {
+    if (!targets || !dist) return UNET_ERR_INVALID;
+    if (!edt_shape_ok(N, C, H, W)) return UNET_ERR_SHAPE;
+    try {
+        std::vector<int> g2((size_t)N * H * W);
+        edt_host(targets, N, C, H, W, g2.data(), dist);
+        return UNET_OK;
+    } catch (const std::bad_alloc&) {
+        return UNET_ERR_NOMEM;
+    } catch (...) {
+        return UNET_ERR_INTERNAL;
+    }
+}
+
+int unet_boundary_fwd(unet_ctx* c, const float* logits, const float* targets, const float* dist,
+                      int N, int C, int H, int W, double* sum, float* loss, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !logits || !targets || !dist || !sum || !loss) return UNET_ERR_INVALID;
+    if (N < 1 || C < 1 || H < 1 || W < 1) return fail(c, UNET_ERR_SHAPE, "bad loss shape");
+    const int64_t hw = (int64_t)H * W;
+    if (int r = boundary_scratch(c, sizeof(float) * (size_t)N * loss_groups(hw))) return r;
+    int r = k_boundary_fwd(logits, targets, dist, N, C, hw, (float*)c->bscr, sum, loss,
+                           (hipStream_t)stream);
+    return r ? fail(c, UNET_ERR_HIP, "boundary_fwd launch %d", r) : UNET_OK;
+    ABI_CATCH(c)
+}
+
+int unet_boundary_bwd(unet_ctx* c, const float* logits, const float* targets, const float* dist,
+                      int N, int C, int H, int W, const float* w, float* dlogits,
+                      unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !logits || !targets || !dist || !w || !dlogits) return UNET_ERR_INVALID;
+    if (N < 1 || C < 1 || H < 1 || W < 1) return fail(c, UNET_ERR_SHAPE, "bad loss shape");
+    int r = k_boundary_bwd(logits, targets, dist, N, C, (int64_t)H * W, w, dlogits,
+                           (hipStream_t)stream);
+    return r ? fail(c, UNET_ERR_HIP, "boundary_bwd launch %d", r) : UNET_OK;
     ABI_CATCH(c)
 }
 

@@ -8,16 +8,17 @@ the logits, and each module below just picks its term:
 * ``DiceLoss``          - soft Dice, per-sample, smooth 1 (models/loss.py:7-24)
 * ``FocalTverskyLoss``  - global TP/FP/FN Tversky index ** gamma (models/loss.py:26-46)
 
-``BoundaryLoss`` (models/loss.py:48-66) needs a Euclidean distance transform of each
-target on the host (scipy) exactly like the reference; it is off the hot path (its weight
-is 0 in every BASELINE config) and is computed with plain torch ops + scipy here.
+``BoundaryLoss`` (models/loss.py:48-66) needs the Euclidean distance transform of each
+target.  On GPU tensors it runs on the device (``unet_hip.boundary_loss``: an exact distance
+transform in HIP, bit-equal to scipy's, one loss and one dlogits kernel, no host sync); CPU
+tensors keep the reference's scipy + torch path.
 """
 import numpy as np
 import scipy.ndimage as nd
 import torch
 import torch.nn as nn
 
-from unet_hip import seg_losses
+from unet_hip import boundary_loss, distance_maps, seg_losses
 
 
 class BCEWithLogitsLoss(nn.Module):
@@ -55,6 +56,8 @@ class FocalTverskyLoss(nn.Module):
 
 def _distance_maps(targets):
     """EDT of the background of each (binarised) target, float32 (N, 1, H, W) on targets' device."""
+    if targets.is_cuda:
+        return distance_maps(targets)
     t = targets.detach().cpu().numpy().astype(np.uint8)
     out = np.stack([nd.distance_transform_edt(1 - t[b, 0]) for b in range(t.shape[0])])
     return torch.from_numpy(out[:, None].astype(np.float32)).to(targets.device)
@@ -64,6 +67,8 @@ class BoundaryLoss(nn.Module):
     """mean_b mean_hw |sigmoid(x) - t| * EDT(1 - t)   (reference models/loss.py:48-66)."""
 
     def forward(self, logits, targets):
+        if logits.is_cuda:
+            return boundary_loss(logits, targets)
         dist = _distance_maps(targets)
         per = (torch.abs(torch.sigmoid(logits) - targets) * dist).flatten(1).mean(1)
         return per.mean()

@@ -10,6 +10,9 @@
   ``[bce, dice, focal]``; its backward takes the incoming gradient of that vector as the
   per-term weights, so ``bce_ratio*l[0] + dice_ratio*l[1] + ...`` (utils/trainer.py:90)
   differentiates into ONE dlogits kernel with no host synchronisation.
+* ``BoundaryLossFunction`` - BoundaryLoss (models/loss.py:48-66) over a distance map computed
+  on the device (``distance_maps``: the exact Euclidean distance transform kernels); its
+  backward is one dlogits kernel weighted by the incoming gradient, again with no host sync.
 """
 import torch
 import torch.distributed as dist
@@ -77,3 +80,56 @@ def seg_losses(logits, targets, alpha=0.4, beta=0.6, gamma=2.0, group=None):
         raise ValueError(f"targets {tuple(targets.shape)} != logits {tuple(logits.shape)}")
     return SegLossFunction.apply(logits, targets, rt, float(alpha), float(beta), float(gamma),
                                  group)
+
+
+class BoundaryLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, dist, rt):
+        logits = logits.contiguous()
+        loss = rt.boundary_fwd(logits, targets, dist)
+        ctx.save_for_backward(logits, targets, dist)
+        ctx.rt = rt
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, targets, dist = ctx.saved_tensors
+        w = g.contiguous().float().reshape(1)
+        return ctx.rt.boundary_bwd(logits, targets, dist, w), None, None, None
+
+
+def _boundary_runtime(t, what):
+    if t.device.type != "cuda":
+        raise HipUnavailable(f"{what} runs on the HIP path only (got a CPU tensor)")
+    from .runtime import UNetRuntime
+    return UNetRuntime.get(t.device)
+
+
+def distance_maps(targets):
+    """float32 (N, 1, H, W): Euclidean distance of every pixel to the nearest pixel of
+    targets[:, 0] whose uint8 cast is 1 -- bit for bit
+    ``scipy.ndimage.distance_transform_edt(1 - targets.astype(np.uint8)[n, 0])`` cast to
+    float32 (models/loss.py:55-61), including scipy's result for a sample without any such
+    pixel.  Computed on the device, on the current stream; max(H, W) <= 2048."""
+    rt = _boundary_runtime(targets, "distance_maps")
+    if targets.dim() != 4:
+        raise ValueError(f"targets must be (N, C, H, W), got {tuple(targets.shape)}")
+    return rt.edt(targets.detach().contiguous().float())
+
+
+def boundary_loss(logits, targets, dist=None):
+    """mean_n mean_hw |sigmoid(logits[n, 0]) - targets[n, 0]| * dist[n] (models/loss.py:48-66)
+    on the HIP path.  dist: a precomputed ``distance_maps(targets)``; None computes it."""
+    rt = _boundary_runtime(logits, "boundary_loss")
+    if targets.shape != logits.shape:
+        raise ValueError(f"targets {tuple(targets.shape)} != logits {tuple(logits.shape)}")
+    targets = targets.detach().contiguous().float()
+    if dist is None:
+        dist = rt.edt(targets)
+    else:
+        N, _, H, W = logits.shape
+        if tuple(dist.shape) != (N, 1, H, W) or dist.device != logits.device:
+            raise ValueError(f"dist must be {(N, 1, H, W)} on {logits.device}, got "
+                             f"{tuple(dist.shape)} on {dist.device}")
+        dist = dist.detach().contiguous().float()
+    return BoundaryLossFunction.apply(logits, targets, dist, rt)

@@ -129,6 +129,35 @@ class UNetRuntime:
         _lib.check(rc, self.ctx, "unet_loss_bwd")
         return d
 
+    def edt(self, targets):
+        """dist (N, 1, H, W): exact Euclidean distance transform of targets[:, 0] (unet_edt)."""
+        N, C, H, W = targets.shape
+        dist = torch.empty((N, 1, H, W), dtype=torch.float32, device=targets.device)
+        rc = self.lib.unet_edt(self.ctx, _lib.ptr(targets), N, C, H, W, _lib.ptr(dist),
+                               _lib.stream_ptr(targets.device))
+        _lib.check(rc, self.ctx, "unet_edt")
+        return dist
+
+    def boundary_fwd(self, logits, targets, dist):
+        """BoundaryLoss value (0-dim fp32) of logits / targets / dist (unet_boundary_fwd)."""
+        N, C, H, W = logits.shape
+        s = torch.empty(1, dtype=torch.float64, device=logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        rc = self.lib.unet_boundary_fwd(self.ctx, _lib.ptr(logits), _lib.ptr(targets), _lib.ptr(dist),
+                                        N, C, H, W, _lib.ptr(s), _lib.ptr(loss),
+                                        _lib.stream_ptr(logits.device))
+        _lib.check(rc, self.ctx, "unet_boundary_fwd")
+        return loss
+
+    def boundary_bwd(self, logits, targets, dist, w):
+        N, C, H, W = logits.shape
+        d = torch.empty_like(logits)
+        rc = self.lib.unet_boundary_bwd(self.ctx, _lib.ptr(logits), _lib.ptr(targets), _lib.ptr(dist),
+                                        N, C, H, W, _lib.ptr(w), _lib.ptr(d),
+                                        _lib.stream_ptr(logits.device))
+        _lib.check(rc, self.ctx, "unet_boundary_bwd")
+        return d
+
     def adamw(self, params, grads, m, v, step, lr, beta1, beta2, eps, wd, grad_scale=1.0):
         rc = self.lib.unet_adamw(self.ctx, _lib.ptr(params), _lib.ptr(grads), _lib.ptr(m), _lib.ptr(v),
                                  params.numel(), step, float(lr), float(beta1), float(beta2),

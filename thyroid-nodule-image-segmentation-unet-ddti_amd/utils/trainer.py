@@ -22,9 +22,10 @@ What runs where (MI355X-first):
   global), runs per-rank BatchNorm as DataParallel's replicas do, gets the gathered batch's
   losses (incl. FocalTversky's global TP/FP/FN) and the summed gradients; epoch meters and
   confusion counts are summed over ranks.
-* BoundaryLoss keeps the reference's host EDT and is only evaluated when its ratio != 0
-  (the reference evaluates it every step even at ratio 0; 0 * finite == 0, so skipping it
-  changes no number).
+* BoundaryLoss runs on the device too (``unet_hip.boundary_loss``: exact distance transform,
+  loss and dlogits kernels, no host sync) and is only evaluated when its ratio != 0 (the
+  reference evaluates it every step even at ratio 0; 0 * finite == 0, so skipping it changes
+  no number).
 """
 import os
 import random

@@ -59,6 +59,12 @@ Fixtures (all float64 statistics computed from fp32 results):
                     over two replicas (shards 2 + 1), BCE + Dice of the gathered logits, two
                     AdamW steps (lr 1e-4): logits, losses, grad norm/sum/samples, param
                     samples, running stats per step; eval logits with replica 0's buffers.
+  boundary_32.npz   the reference BoundaryLoss (models/loss.py:48-66) under torch autograd on
+                    the CPU: x (3, 1, 32, 48); t = an ordinary binary blob, an all-zero sample
+                    (scipy's empty-mask result) and a soft mixup lam a + (1 - lam) b of two
+                    blobs whose overlap is exactly 1.0 while the rest is below 1 (only the
+                    overlap is a feature site); dist as models/loss.py:55-61 computes it, cast
+                    to float32; loss; dlogits.
   init_seed42.json  the reference modules' own initialisation after torch.manual_seed(42):
                     state_dict names, shapes and the SHA-256 of every tensor's bytes for
                     model.py UNet(1, 1) (unet), mod.py UNet(1, 1, 64, 3) (mod_64_3) and mod.py
@@ -79,6 +85,7 @@ sys.path.insert(0, REF)
 from models.model import UNet as RefUNet  # noqa: E402  (reference)
 from models.loss import DiceLoss as RefDice  # noqa: E402  (reference)
 from models.loss import FocalTverskyLoss as RefFocal  # noqa: E402  (reference, models/loss.py:26-46)
+from models.loss import BoundaryLoss as RefBoundary  # noqa: E402  (reference, models/loss.py:48-66)
 from models.mod import UNet as RefModUNet  # noqa: E402  (reference, models/mod.py:9-66)
 from models.mod import ResUNet as RefResUNet  # noqa: E402  (reference, models/mod.py:88-131)
 
@@ -527,6 +534,31 @@ def case_mod_c4_64():
     np.savez_compressed(os.path.join(OUT, "mod_c4_64.npz"), **out)
 
 
+def _blob(H, W, cy, cx, ry, rx):
+    yy, xx = np.mgrid[0:H, 0:W]
+    return ((((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2) <= 1.0).astype(np.float32)
+
+
+def case_boundary_32():
+    import scipy.ndimage as nd
+    H, Wd = 32, 48
+    x = torch.from_numpy(W.make_input(11, 3, 1, H, Wd)) * 4 - 2  # logits of both signs
+    lam = np.float32(0.375)  # exact in binary: lam + (1 - lam) == 1.0 in float32
+    t = np.zeros((3, 1, H, Wd), np.float32)
+    t[0, 0] = _blob(H, Wd, 14, 20, 7, 11)
+    t[2, 0] = lam * _blob(H, Wd, 12, 17, 8, 9) + (np.float32(1) - lam) * _blob(H, Wd, 19, 27, 7, 10)
+    assert (t[2] == 1.0).any() and ((t[2] > 0) & (t[2] < 1)).any() and not t[1].any()
+    t = torch.from_numpy(t)
+    xr = x.clone().requires_grad_(True)
+    loss = RefBoundary()(xr, t)
+    loss.backward()
+    gt = t.numpy().astype(np.uint8)  # models/loss.py:55,59-61
+    dist = np.stack([nd.distance_transform_edt(1 - gt[b, 0]) for b in range(3)])[:, None]
+    np.savez_compressed(os.path.join(OUT, "boundary_32.npz"), x=x.numpy(), t=t.numpy(),
+                        dist=dist.astype(np.float32), loss=np.float32(loss.item()),
+                        dlogits=xr.grad.numpy())
+
+
 def tensor_digest(t):
     """SHA-256 of a tensor's dtype, shape and bytes (tests/_helpers.py restates it)."""
     import hashlib
@@ -568,6 +600,7 @@ if __name__ == "__main__":
     case_mod_narrow_64()
     case_dp_eval_64()
     case_dp_modres_64()
+    case_boundary_32()
     case_init_seed42()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
