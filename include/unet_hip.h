@@ -199,7 +199,8 @@ int unet_boundary_bwd(unet_ctx* ctx, const float* logits, const float* targets, 
                       int N, int C, int H, int W, const float* w, float* dlogits,
                       unet_stream_t stream);
 
-/* AdamW over flat arenas of n floats (one launch for all parameter tensors).
+/* AdamW over flat arenas of n floats (one launch for all parameter tensors; any part of a
+ * parameter arena, too: the weight images of unet_adamw_repack are dropped if it overlaps theirs).
  * Hyper-parameters are the optimizer's Python floats (double); the library forms
  * 1 - lr*wd, 1 - beta1, 1 - beta2, -lr/(1 - beta1^step) and (1 - beta2^step)**0.5 in
  * double and rounds each to float once, as torch does (optim/adam.py _single_tensor_adam).
@@ -212,16 +213,30 @@ int unet_adamw(unet_ctx* ctx, float* params, const float* grads, float* exp_avg,
  * arena of this context (n == the unet_num_params float count), fused with the weight repack
  * the next forward needs: every 3x3 conv / ConvT weight tile is updated and packed into the
  * context's own GEMM images in one pass, the other tensors are updated elementwise.  Results
- * are bit-identical to unet_adamw.  The next unet_forward on the same `params` pointer reads
- * those images instead of repacking, until unet_params_changed (the caller changed the
- * parameters by other means: load_state_dict, another optimizer) or the next repack.  A
- * training forward that read them refuses its backward (UNET_ERR_INVALID) if they were rewritten
- * in between.  Another n, or a channel-padded network, runs the plain unet_adamw. */
+ * are bit-identical to unet_adamw.  The context holds ONE set of images: those of the arena
+ * repacked last.  The next unet_forward on the same `params` pointer reads them instead of
+ * repacking; a forward on any other arena (another model of this configuration) packs into
+ * its own workspace, as every forward did before.  The images stop being read once
+ *   - the arena is declared written by other means (unet_arena_changed, unet_params_changed:
+ *     load_state_dict, another optimizer, a broadcast),
+ *   - unet_adamw on this context writes into any part of the arena,
+ *   - unet_set_option changes a value (which images exist depends on the options), or
+ *   - the next repack replaces them.
+ * Each training forward records, with its workspace, whether it read the context's images.
+ * Its unet_backward reads the same ones: the workspace's own, or the context's -- and then
+ * refuses (UNET_ERR_INVALID) only if a later unet_adamw_repack REWROTE them in between.  An
+ * invalidation alone rewrites nothing and never fails a backward.  Another n, or a
+ * channel-padded network, runs the plain unet_adamw. */
 int unet_adamw_repack(unet_ctx* ctx, float* params, const float* grads, float* exp_avg,
                       float* exp_avg_sq, int64_t n, int step, double lr, double beta1, double beta2,
                       double eps, double weight_decay, double grad_scale, unet_stream_t stream);
-/* The caller changed the parameter arena outside unet_adamw_repack: the next forward repacks. */
+/* The caller changed the parameter arena outside unet_adamw_repack: the next forward repacks
+ * (whichever arena the context's images belong to). */
 int unet_params_changed(unet_ctx* ctx);
+/* The same, scoped to one arena: the caller wrote into [params, params + n) floats.  The
+ * images are dropped only if they belong to an arena that range overlaps, so a model that
+ * shares this context with others does not cost them their images. */
+int unet_arena_changed(unet_ctx* ctx, const float* params, int64_t n);
 
 /* Mask readout + confusion counts, utils/trainer.py:101-107,217-242, utils/utils.py:225-251.
  * counts (device int64[6]) += {TP, FP, FN, TN} of (sigmoid(logits) > 0.5) vs targets cast to
@@ -270,8 +285,9 @@ int unet_resize_u8(unet_ctx* ctx, const uint8_t* src, int h, int w, float* dst, 
  *   x3_wtile x3_wblocks x3_n64 x3_r3 head_fuse pool_fuse x3_wwaves x3_wwaves1 tile_group
  * Set them between steps, not between a forward and its backward: the workspace plan and
  * which saved images exist depend on them (x3, convt16, the bf16 kernel choices, ...), so
- * unet_backward returns UNET_ERR_INVALID when any option differs from the last training
- * unet_forward's (or when no training forward ran on this context). */
+ * unet_backward returns UNET_ERR_INVALID when any option differs from those of the training
+ * unet_forward that last ran on its workspace (or when none did; the context remembers the
+ * 64 most recent such workspaces). */
 int unet_set_option(unet_ctx* ctx, const char* name, int64_t value);
 int unet_get_option(const unet_ctx* ctx, const char* name, int64_t* value);
 /* i-th option name (0 ..), UNET_ERR_INVALID past the last one; *name is static. */

@@ -567,3 +567,68 @@ def test_dp2_modres_match_dataparallel_golden(golden_dir, tag):
     ev = res[0][3]
     assert rel_max(ev, f[tag + "eval_logits"]) <= 2e-3
     np.testing.assert_array_equal(res[0][3], res[1][3])  # replica 0's buffers on every rank
+
+
+def _wrap_after_step_worker(rank, world, port, q):
+    import sys
+    import traceback
+    for p in (REPO, PKG, os.path.join(REPO, "tests")):
+        sys.path.insert(0, p)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import unet_hip
+        from _helpers import hip_model, inputs
+        from oracle import unet_ref_cpu as O
+        from unet_hip.dist import DistributedUNet
+        dev = torch.device("cuda:0")
+        m = hip_model(O.make_params(42 if rank == 0 else 7), dev)
+        opt = unet_hip.HipAdamW(m.parameters(), lr=1e-3)
+        x, t = inputs(110 + rank, 2, 32, 32)  # its own batch
+        opt.zero_grad()
+        losses = unet_hip.seg_losses(m(x.to(dev)), t.to(dev))
+        (losses[0] + losses[1]).backward()
+        opt.step()  # fused: the context now holds the images of this rank's own weights
+        DistributedUNet(m, opt)  # rank 0's parameters and buffers replace them
+        xe, _ = inputs(112, 2, 32, 32)  # the same input on both ranks
+        m.eval()
+        with torch.no_grad():
+            lg = m(xe.to(dev)).cpu()
+        params = torch.cat([p.detach().reshape(-1) for p in m.parameters()]).cpu()
+        lg0, p0 = lg.clone(), params.clone()
+        dist.broadcast(lg0, src=0)
+        dist.broadcast(p0, src=0)
+        q.put((rank, bool(torch.equal(p0, params)), bool(torch.equal(lg0, lg)),
+               float((lg0 - lg).abs().max() / lg0.abs().max())))
+    except Exception:
+        q.put((rank, "error", traceback.format_exc()))
+        raise
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(600)
+def test_dp2_wrap_after_a_fused_step():
+    """DistributedUNet built AFTER the model took a fused AdamW step: the broadcast writes the
+    parameters through `.data`, which no version counter sees, so the wrapper declares it.
+    Each rank trains one step from its own seed on its own batch, then wraps; rank 1's
+    eval-mode logits of a common input and its parameters must then be rank 0's, bit for bit
+    (without the declaration rank 1 runs on the images of its pre-broadcast weights)."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_wrap_after_step_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted([q.get(timeout=500), q.get(timeout=500)], key=lambda r: r[0])
+    for p in procs:
+        p.join(120)
+    for r in res:
+        assert r[1] != "error", r[2]
+    for p in procs:
+        assert p.exitcode == 0
+    print("rank 1 vs rank 0: params equal", res[1][1], "logits equal", res[1][2],
+          f"max diff {res[1][3]:.2e} of max|ref|")
+    assert res[0][1] and res[1][1], "parameters differ after the broadcast"
+    assert res[1][2], f"rank 1's logits off by {res[1][3]:.2e} of max|ref|"

@@ -272,16 +272,32 @@ struct unet_ctx {
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
     Options opt;
-    // the options of the last training forward: the workspace plan and which saved images
-    // exist (x3, convt16, the bf16 kernels, ...) depend on them, so unet_backward refuses to
-    // run under different ones (it would read saved activations at shifted offsets, or an
-    // up half the forward never wrote)
-    Options fwd_opt;
-    bool fwd_opt_set = false;
+    // what unet_backward must know about the training forward it completes, kept per forward
+    // (keyed by its workspace: one context serves every model of its configuration on the
+    // device, and their forwards and backwards interleave).  A host-side table, not a header
+    // in the workspace itself: reading device memory back would cost a synchronisation.
+    //  * opt: the workspace plan and which saved images exist (x3, convt16, the bf16 kernels,
+    //    ...) depend on the options, so the backward refuses to run under different ones (it
+    //    would read saved activations at shifted offsets, or an up half the forward never wrote)
+    //  * used_pp / pp_gen: whether the forward read the context's weight images instead of
+    //    packing into its workspace, and their generation then
+    struct FwdRec {
+        const void* ws;
+        Options opt;
+        bool used_pp;
+        uint64_t pp_gen;
+        uint64_t seq;
+    };
+    static constexpr size_t MAX_FWD_RECS = 64;  // forwards awaiting a backward; the oldest leaves
+    std::vector<FwdRec> fwd_recs;
+    uint64_t fwd_seq = 0;
     // (r06) weight images written by unet_adamw_repack (AdamW fused into the repack): device
-    // buffers owned by the context, valid for the parameter arena `pp_src` until
-    // unet_params_changed or another repack; pp_gen counts repacks, and a training forward that
-    // read them records the generation its backward must still see
+    // buffers owned by the context, valid (pp_ok) for the parameter arena
+    // [pp_src, pp_src + n_param_floats) under the options they were written with, until that
+    // arena is written otherwise (unet_arena_changed, unet_adamw on an overlapping range,
+    // unet_params_changed), an option changes, or another repack.  pp_gen counts repacks: the
+    // images a forward read stay usable by its backward for as long as the generation stands,
+    // whether or not pp_ok was cleared in between (clearing it rewrites nothing).
     float* pp = nullptr;
     uint16_t* pp3 = nullptr;
     // (r06) per-chunk loss statistics of unet_loss_stats (4 floats per chunk, grown on demand)
@@ -296,8 +312,6 @@ struct unet_ctx {
     const float* pp_src = nullptr;
     bool pp_ok = false;
     uint64_t pp_gen = 0;
-    bool fwd_used_pp = false;
-    uint64_t fwd_pp_gen = 0;
 
     int nconv() const { return (int)conv.size(); }
     int chl[MAX_DEPTH + 1] = {};                           // kernel (padded) channels per level
@@ -1318,17 +1332,47 @@ bool plan_has_pack3(const unet_ctx* c) {
     return false;
 }
 
+// the record of the training forward on workspace `ws` (the latest one: a workspace is reused)
+unet_ctx::FwdRec* find_fwd(unet_ctx* c, const void* ws) {
+    for (auto& r : c->fwd_recs)
+        if (r.ws == ws) return &r;
+    return nullptr;
+}
+
+unet_ctx::FwdRec* note_fwd(unet_ctx* c, const void* ws) {
+    unet_ctx::FwdRec* r = find_fwd(c, ws);
+    if (!r && c->fwd_recs.size() < unet_ctx::MAX_FWD_RECS) {
+        c->fwd_recs.push_back({});
+        r = &c->fwd_recs.back();
+    }
+    if (!r) r = &*std::min_element(c->fwd_recs.begin(), c->fwd_recs.end(),
+                                   [](const unet_ctx::FwdRec& a, const unet_ctx::FwdRec& b) { return a.seq < b.seq; });
+    r->ws = ws;
+    r->opt = c->opt;
+    r->used_pp = false;
+    r->pp_gen = c->pp_gen;
+    r->seq = ++c->fwd_seq;
+    return r;
+}
+
+// whether [a, a + na) and [b, b + nb) floats share an address
+bool ranges_overlap(const float* a, int64_t na, const float* b, int64_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return na > 0 && nb > 0 && a0 < b0 + 4 * (uint64_t)nb && b0 < a0 + 4 * (uint64_t)na;
+}
+
+// rec: this training forward's record (nullptr: an eval forward, no backward follows)
 int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, const float* x,
-                 float* logits, Plan& p, bool training, hipStream_t s) {
+                 float* logits, Plan& p, bool training, unet_ctx::FwdRec* rec, hipStream_t s) {
     Launcher L{c, s};
     const int H = p.H, W = p.W, D = c->depth, NC = c->nconv();
     // 1. weight images for the row GEMMs: re-packed every call (params may have changed through
     //    the optimizer or load_state_dict; ~0.1 ms of HBM traffic per step at config 2) unless
     //    the fused AdamW of unet_adamw_repack wrote them for exactly these parameters (r06)
     const bool use_pp = c->pp_ok && c->pp_src == prm && c->pp && (!p.pack3 || c->pp3);
-    if (training) {
-        c->fwd_used_pp = use_pp;
-        c->fwd_pp_gen = c->pp_gen;
+    if (rec) {
+        rec->used_pp = use_pp;
+        rec->pp_gen = c->pp_gen;
     }
     if (use_pp) {
         p.pack = c->pp;
@@ -2496,13 +2540,10 @@ int unet_forward(unet_ctx* c, const float* params, float* bn_running, int64_t* b
     make_plan(c, N, H, W, training != 0, (char*)ws, p);
     if (hipSetDevice(c->device) != hipSuccess) return fail(c, UNET_ERR_HIP, "hipSetDevice");
     if (!c->timing) c->ev_used = 0;
-    if (training) {
-        c->fwd_opt = c->opt;
-        c->fwd_opt_set = true;
-    }
+    unet_ctx::FwdRec* rec = training ? note_fwd(c, ws) : nullptr;
     const hipStream_t s = (hipStream_t)stream;
     if (!c->padded)
-        return forward_impl(c, params, bn_running, bn_count, x, logits, p, training != 0, s);
+        return forward_impl(c, params, bn_running, bn_count, x, logits, p, training != 0, rec, s);
     // narrow network: torch-layout arenas -> padded arenas, forward, running stats back
     int r = upload_pad_tables(c, p, s);
     if (!r) r = k_pad_copy(p.ptab, (int)c->pad_params.size(), c->pad_max_numel, params, p.pprm, 1, s);
@@ -2510,7 +2551,7 @@ int unet_forward(unet_ctx* c, const float* params, float* bn_running, int64_t* b
         r = k_pad_copy(p.btab, (int)c->pad_bn.size(), c->pad_bn_max, bn_running, p.pbn, 1, s);
     if (r) return fail(c, UNET_ERR_HIP, "channel-padding expand: %d", r);
     r = forward_impl(c, p.pprm, bn_running ? p.pbn : nullptr, bn_count, x, logits, p,
-                     training != 0, s);
+                     training != 0, rec, s);
     if (r) return r;
     if (training && bn_running &&
         k_pad_copy(p.btab, (int)c->pad_bn.size(), c->pad_bn_max, p.pbn, bn_running, 0, s))
@@ -2524,22 +2565,26 @@ int unet_backward(unet_ctx* c, const float* params, const float* dlogits, float*
     ABI_TRY
     if (!c || !params || !dlogits || !grads || !ws) return c ? fail(c, UNET_ERR_INVALID, "null pointer") : UNET_ERR_INVALID;
     if (!shape_ok(c, N, H, W)) return fail(c, UNET_ERR_SHAPE, "bad shape N=%d H=%d W=%d", N, H, W);
-    if (!c->fwd_opt_set) return fail(c, UNET_ERR_INVALID, "backward without a training forward");
+    const unet_ctx::FwdRec* rec = find_fwd(c, ws);
+    if (!rec) return fail(c, UNET_ERR_INVALID, "backward without a training forward on this workspace");
     for (const OptionDesc& d : OPTION_TABLE)
-        if (c->opt.*d.field != c->fwd_opt.*d.field)
+        if (c->opt.*d.field != rec->opt.*d.field)
             return fail(c, UNET_ERR_INVALID,
                         "option '%s' changed between the training forward (%d) and its backward "
                         "(%d): the workspace plan depends on it",
-                        d.name, c->fwd_opt.*d.field, c->opt.*d.field);
+                        d.name, rec->opt.*d.field, c->opt.*d.field);
     Plan p;
     make_plan(c, N, H, W, true, nullptr, p);
     if (ws_bytes < p.bytes) return fail(c, UNET_ERR_WORKSPACE, "workspace %zu < %zu", ws_bytes, p.bytes);
     make_plan(c, N, H, W, true, (char*)ws, p);
-    if (c->fwd_used_pp) {  // (r06) the forward read the fused AdamW's weight images
-        if (c->pp_gen != c->fwd_pp_gen || !c->pp_ok)
+    // (r06) this forward read the fused AdamW's weight images: they must not have been rewritten
+    // since.  A forward that packed into its own workspace finds its images there, whatever
+    // the context's hold by now.
+    if (rec->used_pp) {
+        if (c->pp_gen != rec->pp_gen)
             return fail(c, UNET_ERR_INVALID,
                         "the weight images the training forward used were rewritten before its "
-                        "backward (unet_adamw_repack / unet_params_changed in between)");
+                        "backward (unet_adamw_repack in between)");
         p.pack = c->pp;
         if (p.pack3) p.pack3 = c->pp3;
     }
@@ -2699,6 +2744,8 @@ int unet_adamw(unet_ctx* c, float* params, const float* grads, float* m, float* 
     a.bc2_sqrt = (float)pow(bc2, 0.5);                // bias_correction2 ** 0.5
     a.eps = (float)eps;                               // .add_(eps)
     a.gscale = (float)gscale;
+    // the plain update packs nothing: the images of an arena it writes into are stale
+    if (c->pp_ok && ranges_overlap(params, n, c->pp_src, c->n_param_floats)) c->pp_ok = false;
     int r = k_adamw(params, grads, m, v, n, a, (hipStream_t)stream);
     return r ? fail(c, UNET_ERR_HIP, "adamw launch %d", r) : UNET_OK;
     ABI_CATCH(c)
@@ -2710,9 +2757,8 @@ int unet_adamw_repack(unet_ctx* c, float* params, const float* grads, float* m, 
     ABI_TRY
     if (!c || !params || !grads || !m || !v || n < 0 || step < 1) return UNET_ERR_INVALID;
     // a narrow (channel-padded) network packs from its padded arena: the plain update, and the
-    // next forward repacks
+    // next forward repacks (unet_adamw drops the images of an arena it writes into)
     if (n != c->n_param_floats || c->padded) {
-        c->pp_ok = false;
         return unet_adamw(c, params, grads, m, v, n, step, lr, b1, b2, eps, wd, gscale, stream);
     }
     if (hipSetDevice(c->device) != hipSuccess) return fail(c, UNET_ERR_HIP, "hipSetDevice");
@@ -2782,6 +2828,12 @@ int unet_params_changed(unet_ctx* c) {
     return UNET_OK;
 }
 
+int unet_arena_changed(unet_ctx* c, const float* params, int64_t n) {
+    if (!c || !params || n < 0) return UNET_ERR_INVALID;
+    if (c->pp_ok && ranges_overlap(params, n, c->pp_src, c->n_param_floats)) c->pp_ok = false;
+    return UNET_OK;
+}
+
 int unet_x3_split_host(const float* v, int64_t n, uint16_t* out) {
     if (!v || !out || n < 0 || n % 32) return UNET_ERR_INVALID;
     for (int64_t i = 0; i < n; ++i) {
@@ -2805,6 +2857,9 @@ int unet_set_option(unet_ctx* c, const char* name, int64_t value) {
     if (!c || !name) return UNET_ERR_INVALID;
     for (const OptionDesc& d : OPTION_TABLE)
         if (strcmp(d.name, name) == 0) {
+            // the weight images are those of the options they were written under (which of
+            // them exist, x3 among them, depends on the options)
+            if (c->opt.*d.field != (int)value) c->pp_ok = false;
             c->opt.*d.field = (int)value;
             return UNET_OK;
         }

@@ -91,6 +91,10 @@ def broadcast_module(module, src=0, group=None):
     with torch.no_grad():
         for t in list(module.parameters()) + list(module.buffers()):
             dist.broadcast(t.data, src=src, group=group)
+    # a write through `.data` moves no version counter: a HIP model that already took a fused
+    # AdamW step would otherwise run on the weight images of its pre-broadcast parameters
+    if hasattr(module, "params_changed"):
+        module.params_changed()
 
 
 class DistributedUNet:

@@ -58,6 +58,18 @@ def arena_owner(flat):
     return st
 
 
+def arena_containing(t):
+    """The _ArenaState whose parameter arena shares an address with tensor `t` (the arena
+    itself, one parameter, a group's run of parameters), or None."""
+    lo = t.data_ptr()
+    hi = lo + 4 * t.numel()
+    for st in list(_ARENAS.values()):
+        base = st.param_arena.data_ptr()
+        if lo < base + 4 * st.param_arena.numel() and base < hi:
+            return st
+    return None
+
+
 class _ArenaState:
     """Flat device arenas shared by the module and the autograd function."""
 
@@ -78,7 +90,7 @@ class _ArenaState:
         self.native_version = None
         _ARENAS[(param_arena.data_ptr(), param_arena.numel())] = self
         # a new arena may reuse the address of one whose images the (shared) context holds
-        rt.params_changed()
+        rt.arena_changed(param_arena)
 
     def version(self):
         return self.param_arena._version + sum(p._version for p, _, _ in self.params)
@@ -87,8 +99,17 @@ class _ArenaState:
         """Tell the native side when the parameters changed outside unet_adamw_repack."""
         v = self.version()
         if v != self.native_version:
-            self.rt.params_changed()
+            # this arena's images only: another model of this configuration (a teacher next to
+            # its student) shares the context and keeps its own
+            self.rt.arena_changed(self.param_arena)
             self.native_version = v
+
+    def images_stale(self):
+        """The arena was written by something neither the version counters nor the native side
+        can see (a `.data` write, a native AdamW through another context): the next forward
+        repacks."""
+        self.rt.arena_changed(self.param_arena)
+        self.native_version = None
 
     def grad_arena_for_backward(self):
         # gradients are written with '=' semantics (zero_grad(set_to_none) is the reference's
@@ -201,8 +222,7 @@ class _HipUNet(nn.Module):
         forward repacks the native weight images."""
         st = self._state
         if st is not None:
-            st.rt.params_changed()
-            st.native_version = None
+            st.images_stale()
 
     @property
     def flat_params(self):

@@ -104,14 +104,22 @@ class HipAdamW(torch.optim.Optimizer):
                     self._flat = {key: (m, v)}
                 # (r06) the whole arena of a HIP model: AdamW fused with its next forward's
                 # weight repack (unet_adamw_repack, bit-identical to unet_adamw)
-                from .module import arena_owner
+                from .module import arena_containing, arena_owner
                 st = arena_owner(fp)
                 if st is not None and fg.numel() == fp.numel():
                     st.rt.adamw_repack(fp, fg, m, v, step, lr, b1, b2, eps, wd, self.grad_scale)
                     st.native_version = st.version()  # the images match the parameters
                 else:
+                    # part of a HIP model's arena (a parameter group, a frozen tensor left out):
+                    # the plain update, through another context than the model's, so the model's
+                    # weight images are declared stale here
                     rt.adamw(fp, fg, m, v, step, lr, b1, b2, eps, wd, self.grad_scale)
+                    st = arena_containing(fp)
+                    if st is not None:
+                        st.images_stale()
             else:
+                from .module import arena_containing
+                stale = {}
                 for p in params:
                     s = self.state[p]
                     if "exp_avg" not in s:
@@ -120,6 +128,11 @@ class HipAdamW(torch.optim.Optimizer):
                     g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                     rt.adamw(p, g, s["exp_avg"], s["exp_avg_sq"], step, lr, b1, b2, eps, wd,
                              self.grad_scale)
+                    st = arena_containing(p)
+                    if st is not None:
+                        stale[id(st)] = st
+                for st in stale.values():  # (as above)
+                    st.images_stale()
             for p in params:
                 self.state[p]["step"] = torch.tensor(float(step))
         return loss

@@ -175,8 +175,16 @@ class UNetRuntime:
         _lib.check(rc, self.ctx, "unet_adamw_repack")
 
     def params_changed(self):
-        """The parameter arena changed outside adamw_repack: the next forward repacks."""
+        """Some parameter arena changed outside adamw_repack: the next forward repacks,
+        whichever model's images this (shared) context holds."""
         _lib.check(self.lib.unet_params_changed(self.ctx), self.ctx, "unet_params_changed")
+
+    def arena_changed(self, arena):
+        """`arena` (a parameter arena or any part of one) was written outside adamw_repack:
+        the context drops its weight images only if they are that arena's
+        (unet_arena_changed), so other models of this configuration keep theirs."""
+        _lib.check(self.lib.unet_arena_changed(self.ctx, _lib.ptr(arena), arena.numel()), self.ctx,
+                   "unet_arena_changed")
 
     # ------------------------------------------------------------------ schedule options
     def set_option(self, name, value):
