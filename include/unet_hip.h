@@ -32,6 +32,10 @@
  *                                                           TP/FP/FN/TN counts
  *   unet_resize_plan / unet_resize_u8  utils/transforms.py:143-156 Resize + ToTensor of the
  *                                   data loader (data/data_loader.py:20-27), on the device
+ *   unet_augment_u8 / _host         main.py:66-91          build_train_transform's Flip -> Rotate
+ *                                   -> AdjustBrightness -> TGCAugment (utils/transforms.py:57-70,
+ *                                   84-93,114-141) of one uint8 plane, on the device
+ *   unet_clahe_u8 / _host           utils/transforms.py:72-81 CLAHE (cv2.createCLAHE) of one plane
  *   unet_bucket_* / unet_stream_wait_bucket   utils/trainer.py:28-30 nn.DataParallel grad
  *                                   reduction -> per-bucket readiness for an RCCL all-reduce
  *                                   overlapped with the rest of the backward pass
@@ -272,6 +276,56 @@ int unet_resize_plan(int in_size, int out_size, int32_t* coeffs, int32_t* bounds
 int unet_resize_u8(unet_ctx* ctx, const uint8_t* src, int h, int w, float* dst, int oh, int ow,
                    const int32_t* kh, const int32_t* bh, int ksh, const int32_t* kv,
                    const int32_t* bv, int ksv, float divisor, unet_stream_t stream);
+
+/* Training augmentations of the input pipeline (main.py:66-91 build_train_transform), applied to
+ * the decoded uint8 planes before unet_resize_u8; bit-identical to the host chain (Pillow's
+ * transposes, Image.rotate(angle, NEAREST, expand=False, fillcolor=0), ImageEnhance.Brightness,
+ * the NumPy TGCAugment and CLAHE of utils/transforms.py).  csrc/aug.h is the shared host / device
+ * source.  The host draws one sample's parameters (same RNG calls as the host chain) and passes
+ * them BY VALUE: nothing is uploaded and nothing synchronises. */
+typedef enum {
+    UNET_ROT_NONE = 0,   /* no rotation (angle % 360 == 0) */
+    UNET_ROT_AFFINE = 1, /* Pillow's 16.16 fixed-point nearest affine transform, coefficients a[] */
+    UNET_ROT_180 = 2,    /* Image.ROTATE_180 */
+    UNET_ROT_90 = 3,     /* Image.ROTATE_90 (counter-clockwise); square planes only */
+    UNET_ROT_270 = 4     /* Image.ROTATE_270; square planes only */
+} unet_rot_mode;
+
+typedef struct {
+    int32_t mode;        /* unet_rot_mode */
+    int32_t flip_h;      /* FLIP_LEFT_RIGHT before the rotation (folded into the source index) */
+    int32_t flip_v;      /* FLIP_TOP_BOTTOM before the rotation */
+    int32_t num_bins;    /* TGC bands (0 = none, at most 64); band i = rows [i bin_h, (i + 1) bin_h),
+                            bin_h = h / num_bins; later rows (and bin_h == 0) keep their values */
+    int32_t a[6];        /* UNET_ROT_AFFINE: xin = (a[2] + y a[1] + x a[0]) >> 16,
+                            yin = (a[5] + y a[4] + x a[3]) >> 16 (int32, arithmetic shift); the
+                            pixel is 0 unless 0 <= xin < w and 0 <= yin < h.  |a[0,1,3,4]| <= 2^16,
+                            |a[2,5]| <= 3 * 2^28 (UNET_ERR_INVALID otherwise) */
+    uint8_t lut[256];    /* brightness table applied to the gathered value (identity = none) */
+    float gain[64];      /* TGC: v = (uint8)trunc(min(max(float(v) * gain[band], 0), 255)) */
+} unet_aug_params;
+
+/* dst (h, w) <- flip, rotate, brightness table and TGC of src (h, w), uint8, dst != src, one
+ * launch.  A mask takes the same call with the identity table and num_bins = 0.  h or w above
+ * 8192, or mode 90 / 270 with h != w, is UNET_ERR_SHAPE; num_bins > 64 is UNET_ERR_UNSUPPORTED.
+ * unet_augment_u8_host is the HOST twin (host pointers, same source). */
+int unet_augment_u8(unet_ctx* ctx, const uint8_t* src, int h, int w, uint8_t* dst,
+                    const unet_aug_params* params, unet_stream_t stream);
+int unet_augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst,
+                         const unet_aug_params* params);
+/* dst (h, w) <- CLAHE of src with clip limit `clip` (<= 0: no clipping) and gx x gy tiles along
+ * x / y, bit-identical to utils.transforms.clahe_u8(img, clip, (gx, gy)): histograms of the tiles
+ * of the plane padded bottom / right with REFLECT_101 to whole tiles, clipped at
+ * max((int)(clip * area / 256), 1) with the excess redistributed, one table per tile, float32
+ * bilinear blend of the four neighbouring tables.  gx * gy > 256 is UNET_ERR_UNSUPPORTED; a
+ * padding larger than the axis can reflect (pad > n - 1) or a side above 8192 is UNET_ERR_SHAPE.
+ * The tile histograms and tables live in a context-owned scratch grown on demand without a host
+ * synchronisation, so issue a context's CLAHE calls on one stream, or order the streams.
+ * unet_clahe_u8_host is the HOST twin. */
+int unet_clahe_u8(unet_ctx* ctx, const uint8_t* src, int h, int w, uint8_t* dst, double clip,
+                  int gx, int gy, unet_stream_t stream);
+int unet_clahe_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, double clip, int gx,
+                       int gy);
 
 /* Kernel-schedule options of a context (new; no reference counterpart).  The defaults are
  * the measured-best schedules; the named alternatives (tiles, LDS-DMA vs register-staged

@@ -1,5 +1,6 @@
 // Host launchers of kernels_misc.hip (internal).
 #pragma once
+#include "../../include/unet_hip.h"
 #include "common.h"
 
 // Weight images of the row GEMMs, every 3x3 conv (kind 0) and ConvTranspose (kind 1) of the
@@ -130,6 +131,17 @@ int k_boundary_fwd(const float* x, const float* t, const float* dist, int N, int
                    float* part, double* sum, float* loss, hipStream_t s);
 int k_boundary_bwd(const float* x, const float* t, const float* dist, int N, int C, int64_t hw,
                    const float* w, float* dx, hipStream_t s);
+// Training augmentations of uint8 planes (kernels_aug.hip; algorithms and rules in aug.h)
+struct ClaheGeom;
+int aug_params_check(const unet_aug_params* p, int h, int w);
+int k_augment_u8(const uint8_t* src, int h, int w, uint8_t* dst, const unet_aug_params& p,
+                 hipStream_t s);
+void augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, const unet_aug_params& p);
+// unet_status of the refusals; fills G
+int clahe_geom(int h, int w, double clip, int gx, int gy, ClaheGeom& G);
+size_t clahe_scratch_bytes(const ClaheGeom& G);
+int k_clahe_u8(const uint8_t* src, uint8_t* dst, const ClaheGeom& G, void* scratch, hipStream_t s);
+void clahe_u8_host(const uint8_t* src, uint8_t* dst, const ClaheGeom& G, int* hist, uint8_t* lut);
 // AdamW scalars, each formed in double and rounded to float once (torch Scalar -> float)
 struct AdamwScalars {
     float decay;     // 1 - lr * weight_decay

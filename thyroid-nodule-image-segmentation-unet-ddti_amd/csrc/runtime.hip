@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/unet_hip.h"
+#include "aug.h"
 #include "edt.h"
 #include "kernels_misc.h"
 #include "x3_split.h"
@@ -309,6 +310,9 @@ struct unet_ctx {
     void* bscr = nullptr;
     size_t bscr_bytes = 0;
     std::vector<void*> bscr_old;
+    // CLAHE scratch (unet_clahe_u8: tile histograms + tables), grown the same way
+    void* ascr = nullptr;
+    size_t ascr_bytes = 0;
     const float* pp_src = nullptr;
     bool pp_ok = false;
     uint64_t pp_gen = 0;
@@ -2466,6 +2470,7 @@ int unet_destroy(unet_ctx* c) {
         if (c->pp3) (void)hipFree(c->pp3);
         if (c->lpart) (void)hipFree(c->lpart);
         if (c->bscr) (void)hipFree(c->bscr);
+        if (c->ascr) (void)hipFree(c->ascr);
         for (void* p : c->bscr_old) (void)hipFree(p);
     }
     delete c;
@@ -2655,18 +2660,23 @@ int unet_loss_bwd(unet_ctx* c, const float* logits, const float* targets, int N,
     ABI_CATCH(c)
 }
 
-// BoundaryLoss scratch of at least `bytes`; never synchronises (see unet_ctx::bscr)
-static int boundary_scratch(unet_ctx* c, size_t bytes) {
-    if (bytes <= c->bscr_bytes) return UNET_OK;
+// A context-owned scratch of at least `bytes`; never synchronises: the outgrown buffer joins
+// bscr_old (see unet_ctx::bscr)
+static int grow_scratch(unet_ctx* c, void*& buf, size_t& have, size_t bytes, const char* what) {
+    if (bytes <= have) return UNET_OK;
     if (hipSetDevice(c->device) != hipSuccess) return fail(c, UNET_ERR_HIP, "hipSetDevice");
-    if (c->bscr) c->bscr_old.reserve(c->bscr_old.size() + 1);
+    if (buf) c->bscr_old.reserve(c->bscr_old.size() + 1);
     void* p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess)
-        return fail(c, UNET_ERR_HIP, "hipMalloc: boundary scratch: %zu bytes", bytes);
-    if (c->bscr) c->bscr_old.push_back(c->bscr);
-    c->bscr = p;
-    c->bscr_bytes = bytes;
+        return fail(c, UNET_ERR_HIP, "hipMalloc: %s scratch: %zu bytes", what, bytes);
+    if (buf) c->bscr_old.push_back(buf);
+    buf = p;
+    have = bytes;
     return UNET_OK;
+}
+
+static int boundary_scratch(unet_ctx* c, size_t bytes) {
+    return grow_scratch(c, c->bscr, c->bscr_bytes, bytes, "boundary");
 }
 
 static bool edt_shape_ok(int N, int C, int H, int W) {
@@ -2999,6 +3009,56 @@ int unet_resize_u8(unet_ctx* c, const uint8_t* src, int h, int w, float* dst, in
                         (hipStream_t)stream);
     return r ? fail(c, UNET_ERR_HIP, "resize launch %d", r) : UNET_OK;
     ABI_CATCH(c)
+}
+
+int unet_augment_u8(unet_ctx* c, const uint8_t* src, int h, int w, uint8_t* dst,
+                    const unet_aug_params* params, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !src || !dst || !params || src == dst) return UNET_ERR_INVALID;
+    if (int r = aug_params_check(params, h, w))
+        return fail(c, r, "augment: plane %d x %d, mode %d, %d TGC bands", h, w, params->mode,
+                    params->num_bins);
+    int r = k_augment_u8(src, h, w, dst, *params, (hipStream_t)stream);
+    return r ? fail(c, UNET_ERR_HIP, "augment launch %d", r) : UNET_OK;
+    ABI_CATCH(c)
+}
+
+int unet_augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst,
+                         const unet_aug_params* params) {
+    if (!src || !dst || !params || src == dst) return UNET_ERR_INVALID;
+    if (int r = aug_params_check(params, h, w)) return r;
+    augment_u8_host(src, h, w, dst, *params);
+    return UNET_OK;
+}
+
+int unet_clahe_u8(unet_ctx* c, const uint8_t* src, int h, int w, uint8_t* dst, double clip, int gx,
+                  int gy, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !src || !dst) return UNET_ERR_INVALID;
+    ClaheGeom G;
+    if (int r = clahe_geom(h, w, clip, gx, gy, G))
+        return fail(c, r, "clahe: plane %d x %d, grid %d x %d", h, w, gx, gy);
+    if (int r = grow_scratch(c, c->ascr, c->ascr_bytes, clahe_scratch_bytes(G), "clahe")) return r;
+    int r = k_clahe_u8(src, dst, G, c->ascr, (hipStream_t)stream);
+    return r ? fail(c, UNET_ERR_HIP, "clahe launch %d", r) : UNET_OK;
+    ABI_CATCH(c)
+}
+
+int unet_clahe_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, double clip, int gx,
+                       int gy) {
+    if (!src || !dst) return UNET_ERR_INVALID;
+    ClaheGeom G;
+    if (int r = clahe_geom(h, w, clip, gx, gy, G)) return r;
+    try {
+        std::vector<int> hist((size_t)gx * gy * 256);
+        std::vector<uint8_t> lut((size_t)gx * gy * 256);
+        clahe_u8_host(src, dst, G, hist.data(), lut.data());
+        return UNET_OK;
+    } catch (const std::bad_alloc&) {
+        return UNET_ERR_NOMEM;
+    } catch (...) {
+        return UNET_ERR_INTERNAL;
+    }
 }
 
 int unet_debug_view(unet_ctx* c, int N, int H, int W, int training, int kind, int index,

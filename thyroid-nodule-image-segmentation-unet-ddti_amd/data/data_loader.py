@@ -9,7 +9,10 @@ the DDTI data is not distributed with the code.
 Device-side transforms: ``MedicalDataset(..., transform=DecodeU8())`` + ``u8_collate``
 keep the host to JPEG decoding; ``DeviceResizeLoader`` then runs the reference's
 Resize + ToTensor (utils/transforms.py:143-156) on the GPU (unet_hip.GpuResizeToTensor,
-bit-identical to the Pillow path) and yields device batches.
+bit-identical to the Pillow path) and yields device batches.  With
+``build_train_transform(cfg, device_augment=True)`` the workers also draw each sample's
+augmentation parameters; the planes carry them (``U8Plane.aug``) to the loader, which applies
+them on the GPU before the resize (unet_augment_u8 / unet_clahe_u8, bit-identical as well).
 """
 import os
 from pathlib import Path
@@ -115,19 +118,22 @@ def dp_collate(collate=None):
 class U8Plane(np.ndarray):
     """A decoded (H, W) uint8 plane that remembers which filter Pillow's resize would use
     for its source image: ``"nearest"`` for palette ("P") and bilevel ("1") images, for
-    which Image.resize replaces BILINEAR by NEAREST, else ``"bilinear"``."""
+    which Image.resize replaces BILINEAR by NEAREST, else ``"bilinear"``.  ``aug``: the
+    sample's augmentation draws for the device to apply (unet_hip.data.AugRecord), or None."""
 
     resample = "bilinear"
+    aug = None
 
     def __array_finalize__(self, obj):
         self.resample = getattr(obj, "resample", "bilinear")
+        self.aug = getattr(obj, "aug", None)
 
-    def __reduce__(self):  # DataLoader workers pickle samples: keep the tag
+    def __reduce__(self):  # DataLoader workers pickle samples: keep the tag and the record
         fn, args, state = super().__reduce__()
-        return fn, args, (state, self.resample)
+        return fn, args, (state, self.resample, self.aug)
 
     def __setstate__(self, st):
-        state, self.resample = st
+        state, self.resample, self.aug = st
         super().__setstate__(state)
 
     @staticmethod
@@ -164,13 +170,15 @@ class DecodeU8:
 
 
 def u8_collate(batch):
-    """Keep variable-size uint8 planes as lists (resized on the device)."""
+    """Keep variable-size uint8 planes as lists (resized on the device); each plane keeps its
+    ``resample`` tag and ``aug`` record."""
     return [b[0] for b in batch], [b[1] for b in batch]
 
 
 class DeviceResizeLoader:
     """Wraps a DataLoader of uint8 (image, mask) lists; yields (N, 1, H, W) fp32 device
-    batches resized + scaled on the GPU exactly like Resize + ToTensor."""
+    batches resized + scaled on the GPU exactly like Resize + ToTensor, after the
+    augmentations recorded on the planes (``U8Plane.aug``), if any."""
 
     def __init__(self, loader, size, device="cuda"):
         from unet_hip import GpuResizeToTensor
@@ -186,4 +194,9 @@ class DeviceResizeLoader:
 
     def __iter__(self):
         for batch in self.loader:
-            yield None if batch is None else self.pipe(*batch)
+            if batch is None:
+                yield None
+                continue
+            images, masks = batch
+            aug = [getattr(im, "aug", None) for im in images]
+            yield self.pipe(images, masks, aug if any(r is not None for r in aug) else None)

@@ -57,6 +57,10 @@ def get_parser(argv=None):
     p.add_argument("--base_filters", default=64, type=int, help="ModUNet / ResUNet (mod.py:13)")
     p.add_argument("--gpu_transforms", action="store_true",
                    help="decode on the host, Resize + ToTensor on the GPU (bit-identical)")
+    p.add_argument("--gpu_augment", action="store_true",
+                   help="implies --gpu_transforms; the training augmentations (Flip, Rotate, "
+                        "AdjustBrightness, TGC, CLAHE) run on the GPU too (bit-identical); the "
+                        "host workers decode and draw the parameters")
     p.add_argument("--depth", default=5, type=int, help="ModUNet / ResUNet (mod.py:14)")
     p.add_argument("--bce_ratio", type=float, default=1)
     p.add_argument("--dice_ratio", type=float, default=0)
@@ -111,13 +115,16 @@ def main(args):
                          "ModUNet and ResUNet (models/mod.py)")
 
     S = args.image_size
-    gpu_tf = args.gpu_transforms and not args.synthetic
+    gpu_tf = (args.gpu_transforms or args.gpu_augment) and not args.synthetic
     if args.synthetic:
         splits = [SyntheticSegmentation(args.synthetic, S, seed=s) for s in range(3)]
     else:
         # main.py:99-100: augmentations on the training split only
         tf = DecodeU8() if gpu_tf else Compose([Resize((S, S)), ToTensor()])
-        train_tf = build_train_transform(config, (S, S), tail=[DecodeU8()] if gpu_tf else None)
+        if args.gpu_augment:
+            train_tf = build_train_transform(config, (S, S), device_augment=True)
+        else:
+            train_tf = build_train_transform(config, (S, S), tail=[DecodeU8()] if gpu_tf else None)
         root = config.dataset_path
         splits = [MedicalDataset(os.path.join(root, d), os.path.join(root, d + "_mask"),
                                  train_tf if d == "train" else tf)

@@ -42,6 +42,14 @@ class UnetCfg(ctypes.Structure):
                 ("base_filters", c_int), ("depth", c_int), ("math", c_int)]
 
 
+class AugParams(ctypes.Structure):
+    """unet_aug_params: one sample's augmentation draws, passed by value to the kernel."""
+    _fields_ = [("mode", ctypes.c_int32), ("flip_h", ctypes.c_int32), ("flip_v", ctypes.c_int32),
+                ("num_bins", ctypes.c_int32), ("a", ctypes.c_int32 * 6),
+                ("lut", ctypes.c_uint8 * 256), ("gain", ctypes.c_float * 64)]
+
+
+ROT_NONE, ROT_AFFINE, ROT_180, ROT_90, ROT_270 = range(5)  # unet_rot_mode
 VARIANT_MODEL = 0  # models/model.py:UNet
 VARIANT_MOD = 1    # models/mod.py:UNet
 VARIANT_RES = 2    # models/mod.py:ResUNet
@@ -97,6 +105,11 @@ SIGNATURES = {
     "unet_resize_plan": (c_int, [c_int, c_int, c_void_p, c_void_p, P(c_int)]),
     "unet_resize_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    "unet_augment_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, P(AugParams), c_void_p]),
+    "unet_augment_u8_host": (c_int, [c_void_p, c_int, c_int, c_void_p, P(AugParams)]),
+    "unet_clahe_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_double, c_int, c_int,
+                              c_void_p]),
+    "unet_clahe_u8_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_double, c_int, c_int]),
     "unet_x3_split_host": (c_int, [c_void_p, c_int64, c_void_p]),
     "unet_x3_split_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "unet_timing_enable": (c_int, [c_void_p, c_int]),

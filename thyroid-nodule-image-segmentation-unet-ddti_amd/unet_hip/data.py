@@ -16,8 +16,19 @@ those modes whatever filter is asked for.  Planes tagged ``resample="nearest"``
 (data.data_loader.DecodeU8 does that) run the same kernel with a one-tap plan: source
 index = int(x0), x0 = s/2 then += s per output pixel (s = in/out, Pillow's accumulated
 double coordinate of ImagingScaleAffine), coefficient 1.0 in 22-bit fixed point.
+
+Training augmentations (``pipe(images, masks, aug=records)``): the host workers draw each
+sample's Flip / Rotate / AdjustBrightness / TGCAugment / CLAHE decisions
+(utils.transforms.RecordAugment, the same RNG calls in the same order as the host chain) into
+an ``AugRecord``; ``unet_augment_u8`` and ``unet_clahe_u8`` apply them to the uint8 planes on
+the device before the resize, bit-identically to Pillow and the NumPy classes
+(tests/test_aug_cpu.py, tests/test_gpu_augment.py).  The rotation matrix is formed here with
+Python's own ``round`` and ``math``, exactly as Pillow's Image.rotate does, and reaches the
+kernel as six 16.16 fixed-point integers.
 """
 import ctypes
+import dataclasses
+import math
 
 import numpy as np
 import torch
@@ -52,14 +63,129 @@ def nearest_plan(in_size, out_size):
     return k, b
 
 
+def _fix(v):
+    """Pillow's FIX (Geometry.c): 16.16 fixed point, rounded half up."""
+    return int(math.floor(v * 65536.0 + 0.5))
+
+
+def rotate_plan(w, h, angle):
+    """(mode, six int32) of Image.rotate(angle, NEAREST, expand=False, fillcolor=0) on a
+    w x h image: Pillow's Python (Image.rotate: transposes for 0 / 180 and, for square images,
+    90 / 270; else the rounded rotation matrix about the centre) and the coefficients its
+    affine_fixed transform derives from that matrix."""
+    angle = angle % 360.0
+    zero = [0] * 6
+    if angle == 0:
+        return _lib.ROT_NONE, zero
+    if angle == 180:
+        return _lib.ROT_180, zero
+    if angle in (90, 270) and w == h:
+        return (_lib.ROT_90 if angle == 90 else _lib.ROT_270), zero
+    r = -math.radians(angle)
+    m = [round(math.cos(r), 15), round(math.sin(r), 15), 0.0,
+         round(-math.sin(r), 15), round(math.cos(r), 15), 0.0]
+    cx, cy = w / 2.0, h / 2.0
+    m[2] = m[0] * -cx + m[1] * -cy + m[2] + cx
+    m[5] = m[3] * -cx + m[4] * -cy + m[5] + cy
+    return _lib.ROT_AFFINE, [_fix(m[0]), _fix(m[1]), _fix(m[2] + m[0] * 0.5 + m[1] * 0.5),
+                             _fix(m[3]), _fix(m[4]), _fix(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+
+
+def brightness_lut(factor):
+    """ImageEnhance.Brightness(img).enhance(factor) of an "L" image as a 256-entry table:
+    Pillow's ImagingBlend of a black image and the image, float32 factor * float32 value,
+    0 at or below 0, 255 at or above 255, truncated in between."""
+    t = np.float32(factor) * np.arange(256, dtype=np.float32)
+    lut = np.zeros(256, np.uint8)
+    mid = (t > 0) & (t < 255)
+    lut[mid] = np.trunc(t[mid]).astype(np.uint8)
+    lut[t >= 255] = 255
+    return lut
+
+
+_IDENTITY_LUT = np.arange(256, dtype=np.uint8)
+
+
+@dataclasses.dataclass
+class AugRecord:
+    """One sample's augmentation draws (utils.transforms.RecordAugment): plain Python values,
+    picklable, in the chain's order Flip -> Rotate -> AdjustBrightness -> TGCAugment -> CLAHE.
+    ``None`` = that augmentation was not drawn (or is not on the device side of the chain)."""
+    flip_h: bool = False
+    flip_v: bool = False
+    angle: float = None        # Rotate: degrees
+    brightness: float = None   # AdjustBrightness: factor
+    tgc: tuple = None          # TGCAugment: the num_bins gains
+    clahe: tuple = None        # CLAHE: (clip, (gx, gy))
+
+    def geometric(self):
+        return self.flip_h or self.flip_v or self.angle is not None
+
+    def params(self, h, w, is_mask):
+        """unet_aug_params of an (h, w) plane, or None when the launch would copy (the mask
+        takes the geometry only)."""
+        point = not is_mask and (self.brightness is not None or self.tgc is not None)
+        if not (self.geometric() or point):
+            return None
+        p = _lib.AugParams()
+        p.flip_h, p.flip_v = int(self.flip_h), int(self.flip_v)
+        if self.angle is not None:
+            p.mode, a = rotate_plan(w, h, self.angle)
+            p.a[:] = a
+        lut = _IDENTITY_LUT
+        if not is_mask and self.brightness is not None:
+            lut = brightness_lut(self.brightness)
+        ctypes.memmove(p.lut, lut.ctypes.data, 256)
+        if not is_mask and self.tgc is not None:
+            if len(self.tgc) > 64:
+                raise _lib.HipError(f"TGC with {len(self.tgc)} bands: UNET_ERR_UNSUPPORTED (64)")
+            p.num_bins = len(self.tgc)
+            p.gain[:len(self.tgc)] = [float(np.float32(g)) for g in self.tgc]
+        return p
+
+
+def _host_plane(a):
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    if a.ndim != 2:
+        raise ValueError("expected an (H, W) uint8 plane")
+    return a
+
+
+def apply_augment_host(plane, record, is_mask=False):
+    """The device chain of ``record`` on one (H, W) uint8 plane through the host hooks
+    (unet_augment_u8_host, unet_clahe_u8_host: the kernels' own source compiled for the host).
+    Keeps the plane's ``resample`` tag."""
+    lib = _lib.load()
+    src = _host_plane(plane)
+    h, w = src.shape
+    p = record.params(h, w, is_mask)
+    if p is not None:
+        dst = np.empty_like(src)
+        _lib.check(lib.unet_augment_u8_host(src.ctypes.data, h, w, dst.ctypes.data,
+                                            ctypes.byref(p)), None, "unet_augment_u8_host")
+        src = dst
+    if not is_mask and record.clahe is not None:
+        clip, (gx, gy) = record.clahe
+        dst = np.empty_like(src)
+        _lib.check(lib.unet_clahe_u8_host(src.ctypes.data, h, w, dst.ctypes.data, float(clip),
+                                          int(gx), int(gy)), None, "unet_clahe_u8_host")
+        src = dst
+    if hasattr(plane, "resample"):
+        src = src.view(type(plane))
+        src.resample = plane.resample
+    return src
+
+
 class GpuResizeToTensor:
-    """Batched Resize((H, W)) + ToTensor of (image, mask) pairs on the device."""
+    """Batched Resize((H, W)) + ToTensor of (image, mask) pairs on the device, after the
+    samples' recorded augmentations when ``aug`` is given."""
 
     def __init__(self, size, device="cuda"):
         self.oh, self.ow = (size, size) if isinstance(size, int) else tuple(size)
         self.device = torch.device(device)
         self.rt = UNetRuntime.get(self.device)
         self._plans = {}
+        self._u8 = None  # intermediate planes of the augmentations (reused, stream-ordered)
 
     def _plan(self, n_in, n_out, nearest=False):
         key = (n_in, n_out, nearest)
@@ -69,15 +195,48 @@ class GpuResizeToTensor:
                                 torch.from_numpy(b).to(self.device), k.shape[1])
         return self._plans[key]
 
-    def resize(self, img, out=None):
-        """One HxW uint8 image -> (oh, ow) fp32 in [0, 1] on the device."""
-        nearest = getattr(img, "resample", "bilinear") == "nearest"
+    def _upload(self, img):
         if isinstance(img, np.ndarray):  # PIL-backed arrays are read-only views
             img = np.require(img, requirements=["C", "W"])
         t = torch.as_tensor(img)
         if t.dtype != torch.uint8 or t.dim() != 2:
             raise ValueError("expected an (H, W) uint8 image (decoded 'L' mode)")
-        t = t.to(self.device, non_blocking=True).contiguous()
+        return t.to(self.device, non_blocking=True).contiguous()
+
+    def _scratch(self, k, h, w):
+        """Intermediate plane k (0 / 1) of the reused device buffer."""
+        n = h * w
+        if self._u8 is None or self._u8.shape[1] < n:
+            self._u8 = torch.empty((2, n), dtype=torch.uint8, device=self.device)
+        return self._u8[k, :n].view(h, w)
+
+    def augment(self, t, rec, is_mask):
+        """The recorded augmentations of one (H, W) uint8 device plane: flip + rotate (+
+        brightness + TGC for an image) in one launch, then CLAHE if drawn.  Returns a view of
+        the reused buffer (valid until the next call) or ``t`` itself when nothing applies."""
+        h, w = t.shape
+        p = rec.params(h, w, is_mask)
+        if p is not None:
+            d = self._scratch(0, h, w)
+            _lib.check(self.rt.lib.unet_augment_u8(
+                self.rt.ctx, _lib.ptr(t), h, w, _lib.ptr(d), ctypes.byref(p),
+                _lib.stream_ptr(self.device)), self.rt.ctx, "unet_augment_u8")
+            t = d
+        if not is_mask and rec.clahe is not None:
+            clip, (gx, gy) = rec.clahe
+            d = self._scratch(1, h, w)
+            _lib.check(self.rt.lib.unet_clahe_u8(
+                self.rt.ctx, _lib.ptr(t), h, w, _lib.ptr(d), float(clip), int(gx), int(gy),
+                _lib.stream_ptr(self.device)), self.rt.ctx, "unet_clahe_u8")
+            t = d
+        return t
+
+    def resize(self, img, out=None, aug=None, is_mask=False):
+        """One HxW uint8 image -> (oh, ow) fp32 in [0, 1] on the device."""
+        nearest = getattr(img, "resample", "bilinear") == "nearest"
+        t = self._upload(img)
+        if aug is not None:
+            t = self.augment(t, aug, is_mask)
         h, w = t.shape
         if out is None:
             out = torch.empty((self.oh, self.ow), dtype=torch.float32, device=self.device)
@@ -89,14 +248,20 @@ class GpuResizeToTensor:
             _lib.stream_ptr(self.device)), self.rt.ctx, "unet_resize_u8")
         return out
 
-    def __call__(self, images, masks=None):
+    def __call__(self, images, masks=None, aug=None):
+        """``aug``: one AugRecord (or None) per sample, applied to the image and the mask
+        before the resize; ``None`` = no augmentation."""
         n = len(images)
+        if aug is None:
+            aug = [None] * n
+        elif len(aug) != n:
+            raise ValueError(f"{len(aug)} augmentation records for {n} images")
         x = torch.empty((n, 1, self.oh, self.ow), dtype=torch.float32, device=self.device)
         for i, im in enumerate(images):
-            self.resize(im, x[i, 0])
+            self.resize(im, x[i, 0], aug[i])
         if masks is None:
             return x
         t = torch.empty_like(x)
         for i, m in enumerate(masks):
-            self.resize(m, t[i, 0])
+            self.resize(m, t[i, 0], aug[i], is_mask=True)
         return x, t

@@ -197,14 +197,20 @@ class TGCAugment:
     def __init__(self, num_bins=10, gain=(0.8, 1.2), p=0.5):
         self.num_bins, self.gain, self.p = num_bins, gain, p
 
-    def __call__(self, img, mask):
+    def draw(self):
+        """The sample's gains (one per band), or None when the augmentation is not applied."""
         if random.random() > self.p:
+            return None
+        return [random.uniform(*self.gain) for _ in range(self.num_bins)]
+
+    def __call__(self, img, mask):
+        gains = self.draw()
+        if gains is None:
             return img, mask
         img_np = np.array(img).astype(np.float32)
         h = img_np.shape[0]
         bin_h = h // self.num_bins
-        for i in range(self.num_bins):
-            g = random.uniform(*self.gain)
+        for i, g in enumerate(gains):
             img_np[i * bin_h:(i + 1) * bin_h] *= g
         img_np = np.clip(img_np, 0, 255).astype(np.uint8)
         return Image.fromarray(img_np), mask
@@ -216,8 +222,12 @@ class CLAHE:
     def __init__(self, clip=2.0, grid=(4, 4), p=0.3):
         self.clip, self.grid, self.p = clip, grid, p
 
+    def draw(self):
+        """Whether the augmentation is applied to this sample."""
+        return not random.random() > self.p
+
     def __call__(self, img, mask):
-        if random.random() > self.p:
+        if not self.draw():
             return img, mask
         return Image.fromarray(clahe_u8(np.array(img), self.clip, self.grid)), mask
 
@@ -228,9 +238,15 @@ class AdjustBrightness:
     def __init__(self, adjust_prob):
         self.adjust_prob = adjust_prob
 
-    def __call__(self, image, mask):
+    def draw(self):
+        """The brightness factor, or None."""
         if random.random() < self.adjust_prob:
-            factor = random.uniform(0.5, 1.5)
+            return random.uniform(0.5, 1.5)
+        return None
+
+    def __call__(self, image, mask):
+        factor = self.draw()
+        if factor is not None:
             image = ImageEnhance.Brightness(image).enhance(factor)
         return image, mask
 
@@ -259,11 +275,16 @@ class Flip:
     def __init__(self, flip_prob):
         self.flip_prob = flip_prob
 
+    def draw(self):
+        """(horizontal, vertical) decisions."""
+        return random.random() < self.flip_prob, random.random() < self.flip_prob
+
     def __call__(self, image, mask):
-        if random.random() < self.flip_prob:
+        flip_h, flip_v = self.draw()
+        if flip_h:
             image = image.transpose(Image.FLIP_LEFT_RIGHT)
             mask = mask.transpose(Image.FLIP_LEFT_RIGHT)
-        if random.random() < self.flip_prob:
+        if flip_v:
             image = image.transpose(Image.FLIP_TOP_BOTTOM)
             mask = mask.transpose(Image.FLIP_TOP_BOTTOM)
         return image, mask
@@ -276,9 +297,15 @@ class Rotate:
     def __init__(self, rotate_prob):
         self.rotate_prob = rotate_prob
 
-    def __call__(self, image, mask):
+    def draw(self):
+        """The angle in degrees, or None."""
         if random.random() < self.rotate_prob:
-            angle = random.uniform(-180, 180)
+            return random.uniform(-180, 180)
+        return None
+
+    def __call__(self, image, mask):
+        angle = self.draw()
+        if angle is not None:
             image = image.rotate(angle, Image.NEAREST, expand=False, fillcolor=0)
             mask = mask.rotate(angle, Image.NEAREST, expand=False, fillcolor=0)
         return image, mask
@@ -327,11 +354,62 @@ class ToTensor:
         return _to_tensor(img), _to_tensor(mask)
 
 
-def build_train_transform(cfg, size=(512, 512), tail=None):
+DEVICE_AUGMENTS = (Flip, Rotate, AdjustBrightness, TGCAugment, CLAHE)
+
+
+class RecordAugment:
+    """Stands in for a run of device-capable transforms (DEVICE_AUGMENTS) at the end of the
+    chain: makes their draws -- each class's own ``draw()``, in chain order, so ``random``
+    advances exactly as if they had run -- without touching a pixel, decodes the pair
+    (data.data_loader.DecodeU8) and attaches the draws to both planes as ``.aug``
+    (unet_hip.data.AugRecord) for the device to apply (unet_hip.GpuResizeToTensor).
+
+    The device applies Flip -> Rotate -> AdjustBrightness -> TGCAugment -> CLAHE, so the run
+    must hold at most one of each, in that order (as build_train_transform's chains do)."""
+
+    def __init__(self, transforms):
+        order = [DEVICE_AUGMENTS.index(type(t)) for t in transforms]  # ValueError: not capable
+        if order != sorted(set(order)):
+            raise ValueError("device augmentations: at most one of each, in the order Flip, "
+                             "Rotate, AdjustBrightness, TGCAugment, CLAHE")
+        self.transforms = list(transforms)
+
+    def draw(self):
+        from unet_hip.data import AugRecord
+        rec = AugRecord()
+        for t in self.transforms:
+            d = t.draw()
+            if isinstance(t, Flip):
+                rec.flip_h, rec.flip_v = d
+            elif isinstance(t, Rotate):
+                rec.angle = d
+            elif isinstance(t, AdjustBrightness):
+                rec.brightness = d
+            elif isinstance(t, TGCAugment):
+                rec.tgc = None if d is None else tuple(d)
+            elif d:
+                rec.clahe = (t.clip, tuple(t.grid))
+        return rec
+
+    def __call__(self, img, mask):
+        from data.data_loader import DecodeU8
+        rec = self.draw()
+        pi, pm = DecodeU8()(img, mask)
+        pi.aug = pm.aug = rec
+        return pi, pm
+
+
+def build_train_transform(cfg, size=(512, 512), tail=None, device_augment=False):
     """main.py:66-91: the optional ultrasound augmentations (cfg.use_elastic / use_speckle /
     use_tgc / use_clahe) around the always-on Flip(0.5), Rotate(0.5), AdjustBrightness(0.5),
     then Resize + ToTensor -- or ``tail`` (e.g. [DecodeU8()]) when the resize runs on the
-    device."""
+    device.
+
+    ``device_augment=True`` (the resize and the augmentations run on the device): the chain
+    is split at its longest suffix of device-capable transforms (DEVICE_AUGMENTS).  The host
+    prefix runs unchanged -- ElasticDeform alone with use_elastic; Flip ... SpeckleNoise with
+    use_speckle, whose float64 noise field stays on the host -- and RecordAugment replaces the
+    suffix and the tail: it draws, decodes and hands the draws to the device."""
     tfs = []
     if getattr(cfg, "use_elastic", False):
         tfs.append(ElasticDeform(p=0.25))
@@ -342,5 +420,12 @@ def build_train_transform(cfg, size=(512, 512), tail=None):
         tfs.append(TGCAugment(p=0.25))
     if getattr(cfg, "use_clahe", False):
         tfs.append(CLAHE(p=0.3))
+    if device_augment:
+        if tail is not None:
+            raise ValueError("device_augment decodes by itself: no tail")
+        k = len(tfs)
+        while k > 0 and isinstance(tfs[k - 1], DEVICE_AUGMENTS):
+            k -= 1
+        return Compose(tfs[:k] + [RecordAugment(tfs[k:])])
     tfs += tail if tail is not None else [Resize(size), ToTensor()]
     return Compose(tfs)
