@@ -1149,20 +1149,21 @@ static int rowgemm_dispatch(const RowGemmArgs& a, int tile, hipStream_t s) {
         return rowgemm_tile<G_IDENT, OP_AFFINE_RELU, E_CONVT, BF>(a, tile, s);
     if (a.amode == G_UP2 && !aff && !dz && a.emode == E_STORE_BN)
         return rowgemm_tile<G_UP2, OP_PLAIN, E_STORE_BN, BF>(a, tile, s);
+    // residual network (models/mod.py:ResUNet): plain operands everywhere (BF: its 64-channel
+    // layers, which the LDS-DMA kernels do not take)
+    if (!aff && !dz) {
+        if (a.amode == G_IDENT && a.emode == E_RESID)
+            return rowgemm_tile<G_IDENT, OP_PLAIN, E_RESID, BF>(a, tile, s);
+        if (a.amode == G_IDENT && a.emode == E_STORE)
+            return rowgemm_tile<G_IDENT, OP_PLAIN, E_STORE, BF>(a, tile, s);
+        if (a.amode == G_CONV3 && a.emode == E_ADD)
+            return rowgemm_tile<G_CONV3, OP_PLAIN, E_ADD, BF>(a, tile, s);
+        if (a.amode == G_IDENT && a.emode == E_CONVT)
+            return rowgemm_tile<G_IDENT, OP_PLAIN, E_CONVT, BF>(a, tile, s);
+        if (a.amode == G_UP2 && a.emode == E_STORE)
+            return rowgemm_tile<G_UP2, OP_PLAIN, E_STORE, BF>(a, tile, s);
+    }
     if constexpr (!BF) {
-        // residual network (models/mod.py:ResUNet): plain operands everywhere
-        if (!aff && !dz) {
-            if (a.amode == G_IDENT && a.emode == E_RESID)
-                return rowgemm_tile<G_IDENT, OP_PLAIN, E_RESID, false>(a, tile, s);
-            if (a.amode == G_IDENT && a.emode == E_STORE)
-                return rowgemm_tile<G_IDENT, OP_PLAIN, E_STORE, false>(a, tile, s);
-            if (a.amode == G_CONV3 && a.emode == E_ADD)
-                return rowgemm_tile<G_CONV3, OP_PLAIN, E_ADD, false>(a, tile, s);
-            if (a.amode == G_IDENT && a.emode == E_CONVT)
-                return rowgemm_tile<G_IDENT, OP_PLAIN, E_CONVT, false>(a, tile, s);
-            if (a.amode == G_UP2 && a.emode == E_STORE)
-                return rowgemm_tile<G_UP2, OP_PLAIN, E_STORE, false>(a, tile, s);
-        }
         if (a.amode == G_CONV3 && a.emode == E_BIAS_RELU_STATS)
             return aff ? rowgemm_tile<G_CONV3, OP_AFFINE, E_BIAS_RELU_STATS, false>(a, tile, s)
                        : rowgemm_tile<G_CONV3, OP_PLAIN, E_BIAS_RELU_STATS, false>(a, tile, s);
@@ -1319,6 +1320,11 @@ int launch_wgrad(const WgradArgs& a, int tile, hipStream_t s) {
                        : wgradT_tile<G_CONV3, OP_PLAIN, G_IDENT>(a, tile, s);
         if (a.amode == G_IDENT && a.bmode == G_UP2 && aff)
             return wgradT_tile<G_IDENT, OP_AFFINE_RELU, G_UP2>(a, tile, s);
+        // residual network: plain operands (skip 1x1 conv; ConvT of a materialised block output)
+        if (a.amode == G_IDENT && a.bmode == G_IDENT && !aff)
+            return wgradT_tile<G_IDENT, OP_PLAIN, G_IDENT>(a, tile, s);
+        if (a.amode == G_IDENT && a.bmode == G_UP2 && !aff)
+            return wgradT_tile<G_IDENT, OP_PLAIN, G_UP2>(a, tile, s);
         return -1;
     }
     const bool aff = a.ascale != nullptr, dz = a.bcoef != nullptr;

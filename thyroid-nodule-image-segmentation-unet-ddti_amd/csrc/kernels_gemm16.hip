@@ -1108,12 +1108,21 @@ int rowgemm16_tile_dims(int tile, int* bm, int* bn, int* stages) {
 }
 
 // The combinations of the BN -> ReLU network (models/mod.py): conv forward (E_STATS),
-// conv dgrad (E_STORE / E_STORE_BN), ConvT forward (E_CONVT), ConvT dgrad (G_UP2, E_STORE_BN).
+// conv dgrad (E_STORE / E_STORE_BN), ConvT forward (E_CONVT), ConvT dgrad (G_UP2, E_STORE_BN);
+// and of the residual network (mod.py:ResUNet): the 1x1 skip's forward closing the block
+// (G_IDENT, E_RESID) and its input gradient (G_IDENT, E_STORE), conv1's input gradient added
+// to it (G_CONV3, E_ADD), the ConvT input gradient of a materialised block output (G_UP2,
+// E_STORE).
 int launch_rowgemm16(const RowGemmArgs& a, int tile, hipStream_t s) {
     if (a.M < 1 || a.K != gather_taps(a.amode) * a.C || !a.a16 || !a.bt16 || !a.zero16) return -1;
     if (a.ascale || a.acoef || a.arelu) return -1;  // operands arrive prepared (k_to_bf16)
-    if ((a.emode == E_STORE_BN) != (a.ey != nullptr)) return -1;
+    if ((a.emode == E_STORE_BN || a.emode == E_RESID) != (a.ey != nullptr)) return -1;
     if ((a.escale != nullptr) != (a.eshift != nullptr)) return -1;
+    if (a.emode == E_RESID && !a.escale) return -1;
+    if (a.amode == G_IDENT && a.emode == E_RESID) return rg16_tile<G_IDENT, E_RESID>(a, tile, s);
+    if (a.amode == G_IDENT && a.emode == E_STORE) return rg16_tile<G_IDENT, E_STORE>(a, tile, s);
+    if (a.amode == G_CONV3 && a.emode == E_ADD) return rg16_tile<G_CONV3, E_ADD>(a, tile, s);
+    if (a.amode == G_UP2 && a.emode == E_STORE) return rg16_tile<G_UP2, E_STORE>(a, tile, s);
     if (a.amode == G_CONV3 && a.emode == E_STATS) return rg16_tile<G_CONV3, E_STATS>(a, tile, s);
     if (a.amode == G_CONV3 && a.emode == E_STORE) return rg16_tile<G_CONV3, E_STORE>(a, tile, s);
     if (a.amode == G_CONV3 && a.emode == E_STORE_BN) return rg16_tile<G_CONV3, E_STORE_BN>(a, tile, s);
@@ -1124,7 +1133,8 @@ int launch_rowgemm16(const RowGemmArgs& a, int tile, hipStream_t s) {
 
 // Weight gradient from bf16 images: a / b point at uint16 images [pixels][lda] /
 // [pixels][ldb] (aoff / boff must be 0: the images are dense), zero16 at a zeroed page.
-// 3x3 conv (A' G_CONV3, B' G_IDENT) and ConvT (A' G_IDENT, B' G_UP2); no bias column sums.
+// 3x3 conv (A' G_CONV3, B' G_IDENT), ConvT (A' G_IDENT, B' G_UP2) and the residual block's 1x1
+// skip (A', B' G_IDENT: a plain product over pixels); no bias column sums.
 int launch_wgrad16(const WgradArgs& a, int tile, hipStream_t s) {
     if (a.aoff || a.boff || a.ascale || a.bcoef || a.bias_slab || !a.zero16 || a.P < 1) return -1;
     if (tile == 4 || tile == 7) {  // tap-row kernel: 3x3 conv layers, W % 64 == 0 (4: 32x32x16, 4 LDS
@@ -1153,6 +1163,7 @@ int launch_wgrad16(const WgradArgs& a, int tile, hipStream_t s) {
     } while (0)
     if (a.amode == G_CONV3 && a.bmode == G_IDENT) WG16G(G_CONV3, G_IDENT);
     if (a.amode == G_IDENT && a.bmode == G_UP2) WG16G(G_IDENT, G_UP2);
+    if (a.amode == G_IDENT && a.bmode == G_IDENT) WG16G(G_IDENT, G_IDENT);
 #undef WG16G
     return -1;
 }

@@ -89,12 +89,15 @@ int k_head_bwd(const float* y, int C, const float* scale, const float* shift, in
                const float* w, int O, int P, int HW, const float* dlog, float* dout, float* partial,
                float* bnpart, int G, hipStream_t s);
 int k_pack_1x1_t(const float* w, float* wt, int cin, int cout, hipStream_t s);
+// bf16 math: the 1x1 skip weight's bf16 images (RNE), plain Wf[co][ci] and transposed Wt[ci][co]
+int k_pack_1x1_bf16(const float* w, uint16_t* wf, uint16_t* wt, int cin, int cout, hipStream_t s);
 // Residual blocks (models/mod.py:ResUNet): first-block forward with the Cin = 1 skip,
 // backward entry (ReLU mask + BN2 partials), first-block skip weight gradient.
 int k_res_first_fwd(const float* x, const float* ws, const float* z, const float* sc,
                     const float* sh, int64_t P, int C, float* out, int ldo, int offo, hipStream_t s);
+// (d16: also the dense bf16 image of du, the operand of the skip's bf16 dgrad / wgrad)
 int k_res_bwd_prep(float* d, const float* out, int ldo, int offo, const float* z, int64_t P, int C,
-                   float* partial, int G, hipStream_t s);
+                   float* partial, int G, hipStream_t s, uint16_t* d16 = nullptr);
 int k_res_first_wgrad(const float* x, const float* du, int P, int C, float* partial, int G,
                       float* gw, hipStream_t s);
 // Pillow-exact 8-bit bilinear resize + scale (input pipeline, utils/transforms.py:143-156)

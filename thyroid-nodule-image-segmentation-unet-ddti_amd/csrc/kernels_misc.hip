@@ -278,6 +278,19 @@ __global__ void pack_1x1_t_kernel(const float* __restrict__ w, float* __restrict
     }
 }
 
+// bf16 math: the same weight as bf16 images (RNE), plain Wf[co][ci] and transposed Wt[ci][co]
+__global__ void pack_1x1_bf16_kernel(const float* __restrict__ w, __bf16* __restrict__ wf,
+                                     __bf16* __restrict__ wt, int cin, int cout) {
+    const int64_t n = (int64_t)cin * cout;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int ci = (int)(i % cin), co = (int)(i / cin);
+        const __bf16 v = (__bf16)w[i];
+        wf[i] = v;
+        wt[(int64_t)ci * cout + co] = v;
+    }
+}
+
 // Block-level combine of per-thread channel partials.  Threads are laid out as
 // (row group g = tid / tpr, channel quad q = tid % tpr); acc[NV] holds NV quantities per
 // channel-quad.  Writes out[v*C + 4q + j] for row group 0.  smem: 256*NV*4 floats.
@@ -1545,10 +1558,12 @@ __global__ void res_first_fwd_kernel(const float* __restrict__ x, const float* _
 
 // Backward entry of a residual block: du = dout [out > 0] (in place) and the BN2 partials
 // partial[G][2][C] = {sum du, sum du z2} (z2 = conv output before BN2, dense [P][C]).
+// d16 (bf16 math): the dense bf16 image of du as well (RNE, as k_to_bf16).
 __global__ __launch_bounds__(256) void res_bwd_prep_kernel(float* __restrict__ d,
                                                           const float* __restrict__ out, int ldo,
                                                           int offo, const float* __restrict__ z,
-                                                          int64_t P, int C, float* partial) {
+                                                          int64_t P, int C, float* partial,
+                                                          __bf16* __restrict__ d16) {
     __shared__ double smem[256 * 2 * 4];
     const int tpr = C / 4 < 256 ? C / 4 : 256, rpp = 256 / tpr;
     double acc[2][4];
@@ -1574,6 +1589,7 @@ __global__ __launch_bounds__(256) void res_bwd_prep_kernel(float* __restrict__ d
                 acc[1][j] += (double)v[j] * zv[j];
             }
             *pd = v;
+            if (d16) *(bf16x4*)(d16 + m * C + c) = to_bf16x4(v);
         }
         block_combine_d<2>(acc, tpr, C, partial + (int64_t)blockIdx.x * 2 * C + c0, smem,
                            (C - c0) / 4);
@@ -2040,6 +2056,11 @@ int k_pack_1x1_t(const float* w, float* wt, int cin, int cout, hipStream_t s) {
                        cin, cout);
     LAUNCH_CHECK();
 }
+int k_pack_1x1_bf16(const float* w, uint16_t* wf, uint16_t* wt, int cin, int cout, hipStream_t s) {
+    hipLaunchKernelGGL(pack_1x1_bf16_kernel, dim3(grid_for((int64_t)cin * cout)), dim3(256), 0, s, w,
+                       (__bf16*)wf, (__bf16*)wt, cin, cout);
+    LAUNCH_CHECK();
+}
 int k_res_first_fwd(const float* x, const float* ws, const float* z, const float* sc,
                     const float* sh, int64_t P, int C, float* out, int ldo, int offo, hipStream_t s) {
     if (C % 4) return -1;
@@ -2048,10 +2069,10 @@ int k_res_first_fwd(const float* x, const float* ws, const float* z, const float
     LAUNCH_CHECK();
 }
 int k_res_bwd_prep(float* d, const float* out, int ldo, int offo, const float* z, int64_t P, int C,
-                   float* partial, int G, hipStream_t s) {
+                   float* partial, int G, hipStream_t s, uint16_t* d16) {
     if (C % 4) return -1;
     hipLaunchKernelGGL(res_bwd_prep_kernel, dim3(G), dim3(256), 0, s, d, out, ldo, offo, z, P, C,
-                       partial);
+                       partial, (__bf16*)d16);
     LAUNCH_CHECK();
 }
 int k_res_first_wgrad(const float* x, const float* du, int P, int C, float* partial, int G,

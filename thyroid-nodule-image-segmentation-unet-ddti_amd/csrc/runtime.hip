@@ -252,6 +252,7 @@ struct unet_ctx {
     std::vector<BnL> bn;
     std::vector<ConvTL> convt;
     std::vector<int64_t> skip_w, skip_pd;  // per block: 1x1 skip weight, its dgrad image
+    std::vector<int64_t> skip_pf;          // bf16 math: its plain bf16 image (skip_pd: bf16 too)
     int64_t head_w = 0, head_b = 0;
     int64_t n_bn_floats = 0;      // caller's running-stat arena
     int64_t n_pbn_floats = 0;     // padded
@@ -447,6 +448,7 @@ void build_graph(unet_ctx* c) {
     };
     c->skip_w.assign(nb, -1);
     c->skip_pd.assign(nb, -1);
+    c->skip_pf.assign(nb, -1);
     auto block = [&](int b, const std::string& pfx) {
         conv_pair(b, 0, pfx);
         conv_pair(b, 1, pfx);
@@ -547,6 +549,10 @@ void build_graph(unet_ctx* c) {
     for (int b = 1; b < nb && c->res; ++b) {  // transposed skip images for the dgrad
         c->skip_pd[b] = pk;
         pk += ((int64_t)c->conv[2 * b].cin * c->conv[2 * b].cout + 31) / 32 * 32;
+        if (c->bf16) {  // the forward GEMM's bf16 image (f32 reads the parameter itself)
+            c->skip_pf[b] = pk;
+            pk += ((int64_t)c->conv[2 * b].cin * c->conv[2 * b].cout + 31) / 32 * 32;
+        }
     }
     c->pack_floats = pk;
     // gradient buckets: walk the arena from its end (what backward finishes first), open a
@@ -624,6 +630,7 @@ struct Plan {
     float* gdz;    // option dz_in_wgrad: the dz the weight gradient stores for the dgrad
     // bf16 LDS-DMA GEMMs: prepared operand image (dense [pixels][C] bf16) and a zero page
     uint16_t* s16;
+    uint16_t* r16;  // residual network, bf16: scratch image of a block's input (conv1 + skip)
     void* zero16;
     std::vector<uint16_t*> x16;  // training, bf16: per-conv input images kept for the wgrad
     std::vector<uint16_t*> t16;  // training, bf16: per-ConvT input images kept for the wgrad
@@ -1014,7 +1021,7 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
     }
     p.stats = b.take<float>(srows);
     p.stats2 = b.take<float>((int64_t)STAT_G * 2 * c->cmax);
-    p.s16 = nullptr;
+    p.s16 = p.r16 = nullptr;
     p.zero16 = b.take<char>(256);  // zeroed 16-B page: padding taps of the LDS-DMA GEMMs
     if (c->bf16) {
         int64_t n16 = 0;
@@ -1022,6 +1029,8 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
         for (const ConvTL& T : c->convt)
             n16 = std::max(n16, std::max(p.P[T.in_level] * T.cin, p.P[T.in_level - 1] * T.cout));
         p.s16 = b.take<uint16_t>(n16);
+        // (where training keeps the image for an LDS-DMA weight gradient, x16, that one is shared)
+        if (c->res) p.r16 = b.take<uint16_t>(n16);
     }
     p.x16.assign(NC, nullptr);
     for (int i = 0; i < NC && training; ++i)
@@ -1030,7 +1039,7 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
     p.t16.assign(c->convt.size(), nullptr);
     for (size_t k = 0; k < c->convt.size() && training; ++k) {
         const ConvTL& T = c->convt[k];
-        if (!c->res && convt_wg16_on(c, T.cin, T.cout))
+        if (convt_wg16_on(c, T.cin, T.cout))
             p.t16[k] = b.take<uint16_t>(p.P[T.in_level] * T.cin);
     }
     // option x3: weight images, kept input images, one scratch image (dz, the concat
@@ -1390,7 +1399,13 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
             RUN("pack", 0, k_to_x3(p.pack, 32, 0, 32, nullptr, nullptr, 0, c->pack_floats / 32, p.pack3,
                                    32, 0, s));
     }
-    for (int b = 1; b <= 2 * D && c->res && training; ++b)
+    // the residual blocks' 1x1 skip weights: written on every call, next to the conv images
+    // (whichever buffer holds those), so they are never stale
+    for (int b = 1; b <= 2 * D && c->res && c->bf16; ++b)
+        RUN("pack", 0, k_pack_1x1_bf16(prm + c->skip_w[b], (uint16_t*)(p.pack + c->skip_pf[b]),
+                                       (uint16_t*)(p.pack + c->skip_pd[b]), c->conv[2 * b].cin,
+                                       c->conv[2 * b].cout, s));
+    for (int b = 1; b <= 2 * D && c->res && !c->bf16 && training; ++b)
         RUN("pack", 0, k_pack_1x1_t(prm + c->skip_w[b], p.pack + c->skip_pd[b], c->conv[2 * b].cin,
                                     c->conv[2 * b].cout, s));
     // 2. concat affine: identity on the up-sampled half (no BN between ConvT and concat)
@@ -1469,7 +1484,9 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
                 return stats_finalize(c, L, p, i, R, M, training, prm, bn_run, bn_cnt);
             }
             if (rg16_on(c, C.cin, C.cout)) {
-                uint16_t* img = p.x16[i] ? p.x16[i] : p.s16;
+                // (residual network: the block's first conv shares its image with the skip GEMM,
+                // which runs after the second conv has reused the scratch image)
+                uint16_t* img = p.x16[i] ? p.x16[i] : (c->res && C.which == 0) ? p.r16 : p.s16;
                 if (pool16[i] || (up16[i] && skipimg[i])) {
                     // (the max-pool / the ConvT and the max-pool stored the whole image)
                 } else if (up16[i]) {  // the ConvT stored the up half already: convert the skip half
@@ -1544,7 +1561,7 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
             RUN(xlabel("convT_fwd", tile, 100 + k), 2.0 * g.M * g.N * g.K, launch_rowgemm_x3(g, tile, s));
             return 0;
         }
-        if (!c->res && rg16_on(c, T.cin, T.cout)) {
+        if (rg16_on(c, T.cin, T.cout)) {
             uint16_t* img = p.t16[k] ? p.t16[k] : p.s16;
             RUN("prep16", 0, k_to_bf16(g.a, g.lda, g.aoff, T.cin, g.ascale, g.ashift, g.arelu, g.M,
                                        img, s));
@@ -1554,7 +1571,9 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
             // reader of that half in a bf16 training step; skip-first concat, identity affine)
             const int idec = 2 * (D + 1 + k);
             const ConvL& Cd = c->conv[idec];
-            if (c->opt.convt16 && c->skip_first && p.x16[idec] && rg16_on(c, Cd.cin, Cd.cout)) {
+            // (not in the residual network: its max-pool does not write the skip half of that
+            // image)
+            if (c->opt.convt16 && !c->res && c->skip_first && p.x16[idec] && rg16_on(c, Cd.cin, Cd.cout)) {
                 g.out16 = p.x16[idec];
                 up16[idec] = true;
             }
@@ -1592,7 +1611,10 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
         g.aoff = a.off;
         g.C = CL.cin;
         g.amode = G_IDENT;
-        g.bt = prm + c->skip_w[b];  // torch layout [co][ci] is already Bt[n][k]
+        if (c->bf16)
+            g.bt16 = (const uint16_t*)(p.pack + c->skip_pf[b]);
+        else
+            g.bt = prm + c->skip_w[b];  // torch layout [co][ci] is already Bt[n][k]
         g.xcd = xcd_remap_on(c);
         g.out = p.out[b];
         g.ldo = p.ldout[b];
@@ -1603,7 +1625,14 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
         g.offey = p.offy[i2];
         g.escale = p.scale[i2];
         g.eshift = p.shift[i2];
-        const int tile = pick_tile(c, CL.cout, false, false);
+        if (rg16_on(c, CL.cin, CL.cout)) {  // from the image conv1 read: rounded once, read twice
+            use_a16(c, p, g, CL.cin);
+            g.a16 = p.x16[2 * b] ? p.x16[2 * b] : p.r16;
+            const int tile = rg16_tile(c, g);
+            RUN(tlabel16("skip_fwd", tile, b), 2.0 * M * CL.cout * CL.cin, launch_rowgemm16(g, tile, s));
+            return 0;
+        }
+        const int tile = pick_tile(c, CL.cout, false, c->bf16);
         RUN(tlabel("skip_fwd", tile, b), 2.0 * M * CL.cout * CL.cin, launch_rowgemm(g, tile, s));
         return 0;
     };
@@ -2112,7 +2141,7 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
             }
             g.stats = p.part;
         }
-        if (!c->res && rg16_on(c, T.cout, T.cin)) {
+        if (rg16_on(c, T.cout, T.cin)) {
             if (!t16) {
                 RUN("prep16", 0, k_to_bf16(p.dcat[lo], ldo, uo, T.cout, nullptr, nullptr, 0, p.P[lo],
                                            p.s16, s));
@@ -2155,15 +2184,20 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
             const ConvL& CL = c->conv[2 * b];
             const int i1 = 2 * b, i2 = 2 * b + 1;
             const int64_t P = p.P[CL.level];
+            // bf16 math: du's bf16 image with it, where an LDS-DMA skip GEMM reads it (the scratch
+            // image is free until conv2's dz pass, which follows the skip's GEMMs)
+            const bool sk_wg16 = CL.pf >= 0 && p.x16[i1] != nullptr;
+            const bool sk_rg16 = CL.pf >= 0 && dx && rg16_on(c, CL.cout, CL.cin);
             RUN("res_bwd_prep", 0, k_res_bwd_prep(G0, p.out[b], p.ldout[b], p.offout[b], p.y[i2], P,
-                                                  CL.cout, p.part, RED_G, s));
+                                                  CL.cout, p.part, RED_G, s,
+                                                  sk_wg16 || sk_rg16 ? p.s16 : nullptr));
             if (CL.pf < 0) {
                 RUN("skip_wgrad", 2.0 * P * CL.cout,
                     k_res_first_wgrad(p.x_nhwc, G0, (int)P, CL.cout, p.hpart, RED_G,
                                       grads + c->skip_w[b], s));
             } else {
                 Operand a = conv_input(c, p, i1);
-                WgradCfg wc = wgrad_cfg(c, CL.cin, 1, CL.cout, 1, P, false);
+                WgradCfg wc = wgrad_cfg(c, CL.cin, 1, CL.cout, 1, P, c->bf16);
                 WgradArgs w{};
                 w.xcd = xcd_remap_wgrad(c);
                 w.H = H >> CL.level;
@@ -2183,6 +2217,21 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
                 w.pps = wc.pps;
                 w.splits = wc.splits;
                 w.slab = p.slab;
+                w.bf16 = c->bf16;
+                if (sk_wg16) {  // A' = the forward's image of the block input, B' = du's image
+                    w.a = (const float*)p.x16[i1];
+                    w.lda = CL.cin;
+                    w.aoff = 0;
+                    w.b = (const float*)p.s16;
+                    w.zero16 = p.zero16;
+                    w.xcd = xcd16_on(c);
+                    const int t = wg16_tile(c, CL.cin, CL.cout);
+                    int wbm = 0, wbn = 0, wst = 0;
+                    wgrad16g_tile_dims(t, &wbm, &wbn, &wst);
+                    char lb[96];
+                    snprintf(lb, sizeof lb, "skip_wgrad/wg16_%dx%ds%d|%d", wbm, wbn, wst, b);
+                    RUN(lb, 2.0 * P * CL.cin * CL.cout, launch_wgrad16(w, t, s));
+                } else
                 RUN(wlabel("skip_wgrad", wc, b), 2.0 * P * CL.cin * CL.cout, launch_wgrad(w, wc.tile, s));
                 RUN("wgrad_reduce", 0, k_slab_reduce(p.slab, wc.splits, w.Mw, w.Nw, 2, CL.cin, CL.cout,
                                                      grads + c->skip_w[b], s));
@@ -2197,13 +2246,20 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
                 g.lda = CL.cout;
                 g.C = CL.cout;
                 g.amode = G_IDENT;
-                g.bt = p.pack + c->skip_pd[b];
-                g.xcd = xcd_remap_on(c);
+                set_weights(c, g, p.pack + c->skip_pd[b]);
                 g.out = dx;
                 g.ldo = ldx;
                 g.emode = E_STORE;
-                const int tile = pick_tile(c, CL.cin, true, false);
-                RUN(tlabel("skip_dgrad", tile, b), 2.0 * P * CL.cin * CL.cout, launch_rowgemm(g, tile, s));
+                if (sk_rg16) {
+                    use_a16(c, p, g, CL.cout);
+                    const int tile = rg16_tile(c, g);
+                    RUN(tlabel16("skip_dgrad", tile, b), 2.0 * P * CL.cin * CL.cout,
+                        launch_rowgemm16(g, tile, s));
+                } else {
+                    const int tile = pick_tile(c, CL.cin, true, c->bf16);
+                    RUN(tlabel("skip_dgrad", tile, b), 2.0 * P * CL.cin * CL.cout,
+                        launch_rowgemm(g, tile, s));
+                }
             }
             if ((rc = bn_finalize(i2, RED_G))) return rc;
             if ((rc = conv_bwd(i2, G0, G1, CL.cout, true, &R))) return rc;
@@ -2447,7 +2503,8 @@ int unet_create(const unet_cfg* cfg, int device, unet_ctx** out) {
         c->res = c->variant == UNET_VARIANT_RES;
         c->bn_relu = c->variant != UNET_VARIANT_MODEL;
         c->skip_first = c->bn_relu;
-        if (c->bf16 && c->variant != UNET_VARIANT_MOD)  // bf16 GEMMs: mod.py UNet (config 4) only
+        // bf16 GEMMs: the BN -> ReLU networks of models/mod.py (UNet, ResUNet)
+        if (c->bf16 && c->variant != UNET_VARIANT_MOD && c->variant != UNET_VARIANT_RES)
             return UNET_ERR_UNSUPPORTED;
         build_graph(c.get());
         *out = c.release();

@@ -1,7 +1,9 @@
 """CLI entry (mirror of the reference's main.py:17-161) on the HIP UNet path.
 
 Same flags as the reference (``--dataset_path``, ``--checkpoint_path``, ``--bce_ratio`` ...
-``--use_data_parallel``), with three additions: ``--model_type`` picks the network
+``--use_data_parallel``), with four additions (``--mfma {fp32,bf16}`` selects the GEMM
+arithmetic of ModUNet / ResUNet; ``--use_amp_autocast`` stays parsed and ignored):
+``--model_type`` picks the network
 (``ResUNet``: models/mod.py:88-131, what the reference hard-codes at main.py:120-122;
 ``ModUNet``: models/mod.py:9-66; ``UNet``: models/model.py, the BASELINE network and the
 default here; ``--base_filters`` / ``--depth`` for the mod.py ones, default 64 / 5 as
@@ -76,6 +78,9 @@ def get_parser(argv=None):
     p.add_argument("--alpha", type=float, default=2)
     p.add_argument("--use_data_parallel", type=_flag, default=True)
     p.add_argument("--use_amp_autocast", type=_flag, default=False)
+    p.add_argument("--mfma", default="fp32", choices=("fp32", "bf16"),
+                   help="ModUNet / ResUNet: conv GEMM arithmetic (bf16: operands rounded to "
+                        "bf16, f32 accumulate; base_filters 64, 128 or 256)")
     p.add_argument("--mode", choices=["train", "test", "both"], default="test")
     p.add_argument("--image_size", type=int, default=512)
     p.add_argument("--synthetic", type=int, default=0, help="synthetic samples per split")
@@ -149,12 +154,25 @@ def main(args):
             dl = create_dataloader(ds, config, shuffle=(i != 1))
         loaders.append(DeviceResizeLoader(dl, (S, S), config.device) if gpu_tf else dl)
 
+    if args.use_amp_autocast:  # parsed and ignored, as before
+        logger.info("--use_amp_autocast is ignored; the reduced-precision mode of this path is "
+                    "--mfma bf16")
     if args.model_type == "ResUNet":
-        model = ResUNet(base_filters=args.base_filters, depth=args.depth)
+        model = ResUNet(base_filters=args.base_filters, depth=args.depth, mfma_dtype=args.mfma)
     elif args.model_type == "ModUNet":
-        model = ModUNet(base_filters=args.base_filters, depth=args.depth)
+        model = ModUNet(base_filters=args.base_filters, depth=args.depth, mfma_dtype=args.mfma)
+    elif args.mfma != "fp32":
+        raise SystemExit("--mfma bf16: models/model.py UNet has no bf16 path (UNET_ERR_UNSUPPORTED); "
+                         "use --model_type ModUNet or ResUNet")
     else:
         model = UNet()
+    if args.mfma != "fp32":  # a width the library refuses: its message now, no fallback
+        from unet_hip.runtime import UNetRuntime
+        try:
+            UNetRuntime.get(config.device, *model._native_cfg())
+        except Exception as e:
+            raise SystemExit(f"--mfma {args.mfma} with {args.model_type}(base_filters="
+                             f"{args.base_filters}, depth={args.depth}): {e}")
     if config.checkpoint_path and os.path.isfile(config.checkpoint_path):
         model.load_state_dict(torch.load(config.checkpoint_path, weights_only=True))
     n = sum(p.numel() for p in model.parameters() if p.requires_grad)

@@ -322,14 +322,22 @@ class _ResidualBlock(nn.Module):
 class ResUNet(_HipUNet):
     """models/mod.py:88-131 ``ResUNet(in_channels, out_channels, base_filters, depth)``:
     every block is ReLU(conv(x) + skip(x)) with conv = Conv-BN-ReLU-Conv-BN and a bias-free
-    1x1 skip.  Same widths as ``ModUNet`` (f32 GEMMs)."""
+    1x1 skip.  Same widths as ``ModUNet``.
+
+    ``mfma_dtype``: as ``ModUNet``'s -- "fp32" (default) or "bf16" (the 3x3, 1x1 skip and
+    ConvTranspose GEMM operands rounded to bf16, f32 accumulate, everything else f32; real
+    ``base_filters`` 64, 128 or 256; the Cin = 1 first block stays f32)."""
 
     _name = "models.mod.ResUNet"
 
-    def __init__(self, in_channels=1, out_channels=1, base_filters=64, depth=5, **kwargs):
+    def __init__(self, in_channels=1, out_channels=1, base_filters=64, depth=5,
+                 mfma_dtype="fp32", **kwargs):
         super().__init__()
+        if str(mfma_dtype) not in ("fp32", "bf16", "torch.float32", "torch.bfloat16"):
+            raise ValueError(f"mfma_dtype must be 'fp32' or 'bf16', got {mfma_dtype!r}")
         self.in_channels, self.out_channels = in_channels, out_channels
         self.base_filters, self.depth = base_filters, depth
+        self.mfma_dtype = "bf16" if "bf" in str(mfma_dtype) else "fp32"
         # construction (and RNG) order of mod.py:96-115
         self.encoders = nn.ModuleList()
         self.pools = nn.ModuleList()
@@ -352,4 +360,4 @@ class ResUNet(_HipUNet):
 
     def _native_cfg(self):
         return (self.in_channels, self.out_channels, _lib.VARIANT_RES, self.base_filters,
-                self.depth, _lib.MATH_F32)
+                self.depth, _lib.MATH_BF16 if self.mfma_dtype == "bf16" else _lib.MATH_F32)
