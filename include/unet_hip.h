@@ -35,7 +35,11 @@
  *   unet_augment_u8 / _host         main.py:66-91          build_train_transform's Flip -> Rotate
  *                                   -> AdjustBrightness -> TGCAugment (utils/transforms.py:57-70,
  *                                   84-93,114-141) of one uint8 plane, on the device
+ *   unet_augment_noise_u8 / _host   utils/transforms.py:45-54 the same with SpeckleNoise between
+ *                                   AdjustBrightness and TGCAugment (the noise field is the host's)
  *   unet_clahe_u8 / _host           utils/transforms.py:72-81 CLAHE (cv2.createCLAHE) of one plane
+ *   unet_elastic_u8 / _host         utils/transforms.py:15-42 ElasticDeform (cv2.GaussianBlur +
+ *                                   cv2.remap) of an image / mask pair from the host's two fields
  *   unet_bucket_* / unet_stream_wait_bucket   utils/trainer.py:28-30 nn.DataParallel grad
  *                                   reduction -> per-bucket readiness for an RCCL all-reduce
  *                                   overlapped with the rest of the backward pass
@@ -313,6 +317,47 @@ int unet_augment_u8(unet_ctx* ctx, const uint8_t* src, int h, int w, uint8_t* ds
                     const unet_aug_params* params, unet_stream_t stream);
 int unet_augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst,
                          const unet_aug_params* params);
+/* unet_augment_u8 with the reference's SpeckleNoise (utils/transforms.py:45-54) between the
+ * brightness table and the TGC gain: noise holds one float64 draw per OUTPUT pixel (h * w, the
+ * host's np.random.normal field; device memory for unet_augment_noise_u8, host memory for the
+ * _host twin), v = (uint8)trunc(min(max((f + f * noise) * 255.0, 0), 255)), f = float32(v) / 255,
+ * the float64 steps rounded one by one.  noise = NULL gives unet_augment_u8's output bit for bit. */
+int unet_augment_noise_u8(unet_ctx* ctx, const uint8_t* src, int h, int w, uint8_t* dst,
+                          const unet_aug_params* params, const double* noise,
+                          unet_stream_t stream);
+int unet_augment_noise_u8_host(const uint8_t* src, int h, int w, uint8_t* dst,
+                               const unet_aug_params* params, const double* noise);
+
+/* The reference's ElasticDeform (utils/transforms.py:15-42) on the decoded uint8 planes, first in
+ * the chain; bit-identical to utils.transforms.gaussian_blur + remap_linear_u8 / remap_nearest
+ * (csrc/elastic.h is the shared host / device source).  The host draws alpha, sigma and the two
+ * uniform float64 fields (np.random.rand(h, w) twice) and computes the Gaussian taps
+ * (utils.transforms.gaussian_kernel); the rest runs here: u = r * 2 - 1, a separable ksize-tap
+ * float64 blur with REFLECT_101 borders (rows first, every product and sum rounded on its own),
+ * map = (float)(index + blur * alpha), a bilinear gather of the image on 1/32-pixel coordinates
+ * with 15-bit integer weights and a nearest gather of the mask, both with BORDER_REFLECT. */
+typedef struct {
+    int32_t ksize;       /* odd, 1 .. 31 (the reference uses 17) */
+    double k[31];        /* the ksize Gaussian taps */
+    double alpha;        /* displacement scale, finite */
+} unet_elastic_params;
+
+/* img_dst / mask_dst (h, w) <- the deformed img / mask (h, w), uint8, under the one map of the
+ * fields rx, ry (h * w float64 each; device memory, read-only).  img or mask may be NULL (that
+ * plane is skipped, its destination ignored), not both; a destination must differ from its source.
+ * Two launches: the row pass of both fields into a context-owned scratch of 2 h w doubles (grown
+ * on demand without a host synchronisation, as for unet_clahe_u8: one stream per context, or
+ * ordered streams), then column pass + map + gathers per output pixel.  ksize even, below 1 or
+ * above 31, or a non-finite alpha is UNET_ERR_INVALID; a side <= ksize / 2 (REFLECT_101 has
+ * nothing to reflect) or above 8192 is UNET_ERR_SHAPE.  unet_elastic_u8_host is the HOST twin
+ * (host pointers, same source). */
+int unet_elastic_u8(unet_ctx* ctx, const uint8_t* img, const uint8_t* mask, int h, int w,
+                    uint8_t* img_dst, uint8_t* mask_dst, const double* rx, const double* ry,
+                    const unet_elastic_params* params, unet_stream_t stream);
+int unet_elastic_u8_host(const uint8_t* img, const uint8_t* mask, int h, int w, uint8_t* img_dst,
+                         uint8_t* mask_dst, const double* rx, const double* ry,
+                         const unet_elastic_params* params);
+
 /* dst (h, w) <- CLAHE of src with clip limit `clip` (<= 0: no clipping) and gx x gy tiles along
  * x / y, bit-identical to utils.transforms.clahe_u8(img, clip, (gx, gy)): histograms of the tiles
  * of the plane padded bottom / right with REFLECT_101 to whole tiles, clipped at

@@ -20,6 +20,8 @@
 // Point operations.  AdjustBrightness is a 256-entry table (Pillow's ImagingBlend with a black
 // image; built in Python).  TGCAugment multiplies row band y / bin_h by a float32 gain and
 // truncates after clamping to [0, 255] -- NumPy's float32_array *= python_float, clip, astype.
+// SpeckleNoise (between the two, on request: unet_augment_noise_u8) multiplies by one float64
+// draw per output pixel, made on the host; its float64 steps are rounded one by one as well.
 //
 // CLAHE restates utils.transforms.clahe_u8 (cv2.createCLAHE): tile histograms over the plane
 // padded bottom / right with REFLECT_101 to whole tiles (by index reflection), clipped and
@@ -45,10 +47,16 @@ constexpr int CLAHE_MAX_TILES = 256;
 #define AUG_MUL(a, b) __fmul_rn((a), (b))
 #define AUG_ADD(a, b) __fadd_rn((a), (b))
 #define AUG_SUB(a, b) __fsub_rn((a), (b))
+#define AUG_DIV(a, b) __fdiv_rn((a), (b))
+#define AUG_DMUL(a, b) __dmul_rn((a), (b))
+#define AUG_DADD(a, b) __dadd_rn((a), (b))
 #else
 #define AUG_MUL(a, b) ((a) * (b))
 #define AUG_ADD(a, b) ((a) + (b))
 #define AUG_SUB(a, b) ((a) - (b))
+#define AUG_DIV(a, b) ((a) / (b))
+#define AUG_DMUL(a, b) ((a) * (b))
+#define AUG_DADD(a, b) ((a) + (b))
 #endif
 
 // Flat source index of output pixel (x, y) of an h x w plane, -1 for a fill pixel.
@@ -88,6 +96,18 @@ AUG_HD uint8_t aug_gain(uint8_t v, float g) {
     t = t > 0.f ? t : 0.f;  // also a NaN gain -> 0, never an undefined cast
     t = t < 255.f ? t : 255.f;
     return (uint8_t)(int)t;
+}
+
+// SpeckleNoise of one value with its float64 noise draw n: f = float32(v) / 255 (a float32
+// division), then in float64 d = f + f * n, d * 255, clamped to [0, 255] and truncated -- NumPy's
+// float32_array / 255., + float32_array * float64_array, * 255., clip, astype(uint8).
+AUG_HD uint8_t aug_speckle(uint8_t v, double n) {
+    double d = (double)AUG_DIV((float)v, 255.f);
+    d = AUG_DADD(d, AUG_DMUL(d, n));
+    d = AUG_DMUL(d, 255.0);
+    d = d > 0.0 ? d : 0.0;  // also a NaN draw -> 0, never an undefined cast
+    d = d < 255.0 ? d : 255.0;
+    return (uint8_t)(int)d;
 }
 
 // Row y of an h-row plane: its TGC band, or -1 when the row keeps its values (past the last

@@ -1,5 +1,5 @@
 // Device-side training augmentations of uint8 planes (aug.h: algorithms and exactness rules):
-// flip + rotate + brightness + TGC in one gather / point kernel, and CLAHE in three passes
+// flip + rotate + brightness (+ speckle) + TGC in one gather / point kernel, and CLAHE in three passes
 // (tile histograms, one table per tile, per-pixel blend).  Host twins for the CPU tests.
 #include <initializer_list>
 
@@ -12,10 +12,12 @@ constexpr int AUG_BLOCK = 256;
 constexpr int HIST_PIXELS = 2048;  // tile pixels per histogram block (8 per thread)
 
 // One thread per output pixel, consecutive threads along x (coalesced stores; the loads are
-// as coalesced as the rotation allows).  dst != src.
+// as coalesced as the rotation allows).  dst != src.  NOISE: the speckle step with noise[idx].
+template <bool NOISE>
 __global__ __launch_bounds__(AUG_BLOCK) void augment_kernel(const uint8_t* __restrict__ src, int h,
                                                            int w, uint8_t* __restrict__ dst,
-                                                           const unet_aug_params p) {
+                                                           const unet_aug_params p,
+                                                           const double* __restrict__ noise) {
     __shared__ uint8_t lut[256];
     __shared__ float gain[AUG_MAX_BINS];
     lut[threadIdx.x] = p.lut[threadIdx.x];
@@ -26,6 +28,7 @@ __global__ __launch_bounds__(AUG_BLOCK) void augment_kernel(const uint8_t* __res
     const int y = idx / w, x = idx - y * w;
     const int s = aug_source(p, x, y, h, w);
     uint8_t v = lut[s < 0 ? 0 : src[s]];
+    if (NOISE) v = aug_speckle(v, noise[idx]);
     const int band = aug_band(y, h, p.num_bins);
     if (band >= 0) v = aug_gain(v, gain[band]);
     dst[idx] = v;
@@ -109,18 +112,24 @@ int aug_params_check(const unet_aug_params* p, int h, int w) {
 }
 
 int k_augment_u8(const uint8_t* src, int h, int w, uint8_t* dst, const unet_aug_params& p,
-                 hipStream_t s) {
-    hipLaunchKernelGGL(augment_kernel, dim3((h * w + AUG_BLOCK - 1) / AUG_BLOCK), dim3(AUG_BLOCK), 0,
-                       s, src, h, w, dst, p);
+                 hipStream_t s, const double* noise) {
+    const dim3 grid((h * w + AUG_BLOCK - 1) / AUG_BLOCK);
+    if (noise)
+        hipLaunchKernelGGL(augment_kernel<true>, grid, dim3(AUG_BLOCK), 0, s, src, h, w, dst, p, noise);
+    else
+        hipLaunchKernelGGL(augment_kernel<false>, grid, dim3(AUG_BLOCK), 0, s, src, h, w, dst, p,
+                           noise);
     return (int)hipGetLastError();
 }
 
-void augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, const unet_aug_params& p) {
+void augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, const unet_aug_params& p,
+                     const double* noise) {
     for (int y = 0; y < h; ++y) {
         const int band = aug_band(y, h, p.num_bins);
         for (int x = 0; x < w; ++x) {
             const int s = aug_source(p, x, y, h, w);
             uint8_t v = p.lut[s < 0 ? 0 : src[s]];
+            if (noise) v = aug_speckle(v, noise[y * w + x]);
             if (band >= 0) v = aug_gain(v, p.gain[band]);
             dst[y * w + x] = v;
         }

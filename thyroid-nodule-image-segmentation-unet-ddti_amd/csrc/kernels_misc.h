@@ -137,14 +137,26 @@ int k_boundary_bwd(const float* x, const float* t, const float* dist, int N, int
 // Training augmentations of uint8 planes (kernels_aug.hip; algorithms and rules in aug.h)
 struct ClaheGeom;
 int aug_params_check(const unet_aug_params* p, int h, int w);
+// noise: one float64 SpeckleNoise draw per output pixel (h * w), or null for none
 int k_augment_u8(const uint8_t* src, int h, int w, uint8_t* dst, const unet_aug_params& p,
-                 hipStream_t s);
-void augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, const unet_aug_params& p);
+                 hipStream_t s, const double* noise = nullptr);
+void augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, const unet_aug_params& p,
+                     const double* noise = nullptr);
 // unet_status of the refusals; fills G
 int clahe_geom(int h, int w, double clip, int gx, int gy, ClaheGeom& G);
 size_t clahe_scratch_bytes(const ClaheGeom& G);
 int k_clahe_u8(const uint8_t* src, uint8_t* dst, const ClaheGeom& G, void* scratch, hipStream_t s);
 void clahe_u8_host(const uint8_t* src, uint8_t* dst, const ClaheGeom& G, int* hist, uint8_t* lut);
+// ElasticDeform of uint8 planes (kernels_elastic.hip; algorithm and rules in elastic.h).  tmp
+// holds elastic_scratch_bytes(h, w); img / mask (with their destinations) may be null
+int elastic_check(const unet_elastic_params* p, int h, int w);  // unet_status of the refusals
+size_t elastic_scratch_bytes(int h, int w);
+int k_elastic_u8(const uint8_t* img, const uint8_t* mask, int h, int w, uint8_t* img_dst,
+                 uint8_t* mask_dst, const double* rx, const double* ry, const unet_elastic_params& p,
+                 double* tmp, hipStream_t s);
+void elastic_u8_host(const uint8_t* img, const uint8_t* mask, int h, int w, uint8_t* img_dst,
+                     uint8_t* mask_dst, const double* rx, const double* ry,
+                     const unet_elastic_params& p, double* tmp);
 // AdamW scalars, each formed in double and rounded to float once (torch Scalar -> float)
 struct AdamwScalars {
     float decay;     // 1 - lr * weight_decay

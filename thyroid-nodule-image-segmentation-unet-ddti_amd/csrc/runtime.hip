@@ -314,6 +314,9 @@ struct unet_ctx {
     // CLAHE scratch (unet_clahe_u8: tile histograms + tables), grown the same way
     void* ascr = nullptr;
     size_t ascr_bytes = 0;
+    // ElasticDeform scratch (unet_elastic_u8: the row pass of both fields), grown the same way
+    void* escr = nullptr;
+    size_t escr_bytes = 0;
     const float* pp_src = nullptr;
     bool pp_ok = false;
     uint64_t pp_gen = 0;
@@ -2521,13 +2524,14 @@ int unet_destroy(unet_ctx* c) {
     if (!c) return UNET_ERR_INVALID;
     for (auto e : c->bucket_ev) (void)hipEventDestroy(e);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->pp || c->pp3 || c->lpart || c->bscr) {
+    if (c->pp || c->pp3 || c->lpart || c->bscr || c->ascr || c->escr) {
         (void)hipSetDevice(c->device);
         if (c->pp) (void)hipFree(c->pp);
         if (c->pp3) (void)hipFree(c->pp3);
         if (c->lpart) (void)hipFree(c->lpart);
         if (c->bscr) (void)hipFree(c->bscr);
         if (c->ascr) (void)hipFree(c->ascr);
+        if (c->escr) (void)hipFree(c->escr);
         for (void* p : c->bscr_old) (void)hipFree(p);
     }
     delete c;
@@ -3086,6 +3090,66 @@ int unet_augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst,
     if (int r = aug_params_check(params, h, w)) return r;
     augment_u8_host(src, h, w, dst, *params);
     return UNET_OK;
+}
+
+int unet_augment_noise_u8(unet_ctx* c, const uint8_t* src, int h, int w, uint8_t* dst,
+                          const unet_aug_params* params, const double* noise,
+                          unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !src || !dst || !params || src == dst) return UNET_ERR_INVALID;
+    if (int r = aug_params_check(params, h, w))
+        return fail(c, r, "augment: plane %d x %d, mode %d, %d TGC bands", h, w, params->mode,
+                    params->num_bins);
+    int r = k_augment_u8(src, h, w, dst, *params, (hipStream_t)stream, noise);
+    return r ? fail(c, UNET_ERR_HIP, "augment launch %d", r) : UNET_OK;
+    ABI_CATCH(c)
+}
+
+int unet_augment_noise_u8_host(const uint8_t* src, int h, int w, uint8_t* dst,
+                               const unet_aug_params* params, const double* noise) {
+    if (!src || !dst || !params || src == dst) return UNET_ERR_INVALID;
+    if (int r = aug_params_check(params, h, w)) return r;
+    augment_u8_host(src, h, w, dst, *params, noise);
+    return UNET_OK;
+}
+
+// both entry points: which planes are asked for, and whether they may be written
+static bool elastic_args_ok(const uint8_t* img, const uint8_t* mask, const uint8_t* img_dst,
+                            const uint8_t* mask_dst, const double* rx, const double* ry,
+                            const unet_elastic_params* p) {
+    return p && rx && ry && (img || mask) && (!img || (img_dst && img_dst != img)) &&
+           (!mask || (mask_dst && mask_dst != mask));
+}
+
+int unet_elastic_u8(unet_ctx* c, const uint8_t* img, const uint8_t* mask, int h, int w,
+                    uint8_t* img_dst, uint8_t* mask_dst, const double* rx, const double* ry,
+                    const unet_elastic_params* params, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !elastic_args_ok(img, mask, img_dst, mask_dst, rx, ry, params)) return UNET_ERR_INVALID;
+    if (int r = elastic_check(params, h, w))
+        return fail(c, r, "elastic: plane %d x %d, ksize %d", h, w, params->ksize);
+    if (int r = grow_scratch(c, c->escr, c->escr_bytes, elastic_scratch_bytes(h, w), "elastic"))
+        return r;
+    int r = k_elastic_u8(img, mask, h, w, img_dst, mask_dst, rx, ry, *params, (double*)c->escr,
+                         (hipStream_t)stream);
+    return r ? fail(c, UNET_ERR_HIP, "elastic launch %d", r) : UNET_OK;
+    ABI_CATCH(c)
+}
+
+int unet_elastic_u8_host(const uint8_t* img, const uint8_t* mask, int h, int w, uint8_t* img_dst,
+                         uint8_t* mask_dst, const double* rx, const double* ry,
+                         const unet_elastic_params* params) {
+    if (!elastic_args_ok(img, mask, img_dst, mask_dst, rx, ry, params)) return UNET_ERR_INVALID;
+    if (int r = elastic_check(params, h, w)) return r;
+    try {
+        std::vector<double> tmp(2 * (size_t)h * w);
+        elastic_u8_host(img, mask, h, w, img_dst, mask_dst, rx, ry, *params, tmp.data());
+        return UNET_OK;
+    } catch (const std::bad_alloc&) {
+        return UNET_ERR_NOMEM;
+    } catch (...) {
+        return UNET_ERR_INTERNAL;
+    }
 }
 
 int unet_clahe_u8(unet_ctx* c, const uint8_t* src, int h, int w, uint8_t* dst, double clip, int gx,

@@ -13,6 +13,9 @@ bit-identical to the Pillow path) and yields device batches.  With
 ``build_train_transform(cfg, device_augment=True)`` the workers also draw each sample's
 augmentation parameters; the planes carry them (``U8Plane.aug``) to the loader, which applies
 them on the GPU before the resize (unet_augment_u8 / unet_clahe_u8, bit-identical as well).
+``device_augment="all"`` adds ElasticDeform and SpeckleNoise: their float64 fields ride in the
+record through the worker pickle and are uploaded with the planes (unet_elastic_u8 /
+unet_augment_noise_u8).
 """
 import os
 from pathlib import Path

@@ -63,6 +63,10 @@ def get_parser(argv=None):
                    help="implies --gpu_transforms; the training augmentations (Flip, Rotate, "
                         "AdjustBrightness, TGC, CLAHE) run on the GPU too (bit-identical); the "
                         "host workers decode and draw the parameters")
+    p.add_argument("--gpu_augment_all", action="store_true",
+                   help="implies --gpu_augment; ElasticDeform and SpeckleNoise run on the GPU too "
+                        "(bit-identical): the host workers draw their float64 fields and send "
+                        "them with the planes, and touch no pixel")
     p.add_argument("--depth", default=5, type=int, help="ModUNet / ResUNet (mod.py:14)")
     p.add_argument("--bce_ratio", type=float, default=1)
     p.add_argument("--dice_ratio", type=float, default=0)
@@ -120,6 +124,7 @@ def main(args):
                          "ModUNet and ResUNet (models/mod.py)")
 
     S = args.image_size
+    args.gpu_augment = args.gpu_augment or args.gpu_augment_all
     gpu_tf = (args.gpu_transforms or args.gpu_augment) and not args.synthetic
     if args.synthetic:
         splits = [SyntheticSegmentation(args.synthetic, S, seed=s) for s in range(3)]
@@ -127,7 +132,8 @@ def main(args):
         # main.py:99-100: augmentations on the training split only
         tf = DecodeU8() if gpu_tf else Compose([Resize((S, S)), ToTensor()])
         if args.gpu_augment:
-            train_tf = build_train_transform(config, (S, S), device_augment=True)
+            train_tf = build_train_transform(config, (S, S),
+                                             device_augment="all" if args.gpu_augment_all else True)
         else:
             train_tf = build_train_transform(config, (S, S), tail=[DecodeU8()] if gpu_tf else None)
         root = config.dataset_path

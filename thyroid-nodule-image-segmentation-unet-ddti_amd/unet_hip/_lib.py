@@ -49,6 +49,11 @@ class AugParams(ctypes.Structure):
                 ("lut", ctypes.c_uint8 * 256), ("gain", ctypes.c_float * 64)]
 
 
+class ElasticParams(ctypes.Structure):
+    """unet_elastic_params: the Gaussian taps and alpha of one ElasticDeform draw."""
+    _fields_ = [("ksize", ctypes.c_int32), ("k", ctypes.c_double * 31), ("alpha", ctypes.c_double)]
+
+
 ROT_NONE, ROT_AFFINE, ROT_180, ROT_90, ROT_270 = range(5)  # unet_rot_mode
 VARIANT_MODEL = 0  # models/model.py:UNet
 VARIANT_MOD = 1    # models/mod.py:UNet
@@ -107,6 +112,14 @@ SIGNATURES = {
                                c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),
     "unet_augment_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, P(AugParams), c_void_p]),
     "unet_augment_u8_host": (c_int, [c_void_p, c_int, c_int, c_void_p, P(AugParams)]),
+    "unet_augment_noise_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, P(AugParams),
+                                      c_void_p, c_void_p]),
+    "unet_augment_noise_u8_host": (c_int, [c_void_p, c_int, c_int, c_void_p, P(AugParams),
+                                           c_void_p]),
+    "unet_elastic_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, P(ElasticParams), c_void_p]),
+    "unet_elastic_u8_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, P(ElasticParams)]),
     "unet_clahe_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_double, c_int, c_int,
                               c_void_p]),
     "unet_clahe_u8_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_double, c_int, c_int]),

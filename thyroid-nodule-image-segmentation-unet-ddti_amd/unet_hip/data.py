@@ -25,6 +25,14 @@ the device before the resize, bit-identically to Pillow and the NumPy classes
 (tests/test_aug_cpu.py, tests/test_gpu_augment.py).  The rotation matrix is formed here with
 Python's own ``round`` and ``math``, exactly as Pillow's Image.rotate does, and reaches the
 kernel as six 16.16 fixed-point integers.
+
+With ``build_train_transform(cfg, device_augment="all")`` the record also carries the float64
+fields of ElasticDeform (``elastic``: alpha, the 17 Gaussian taps computed in Python, and the
+two ``np.random.rand`` fields) and SpeckleNoise (``speckle``: the ``np.random.normal`` field),
+still drawn on the host so the MT19937 streams stay where they are.  They are uploaded with the
+planes; ``unet_elastic_u8`` deforms image and mask under the one map before everything else,
+and ``unet_augment_noise_u8`` is the point launch with the speckle step between the brightness
+table and the TGC gain (tests/test_elastic_cpu.py, tests/test_gpu_elastic.py).
 """
 import ctypes
 import dataclasses
@@ -117,14 +125,31 @@ class AugRecord:
     brightness: float = None   # AdjustBrightness: factor
     tgc: tuple = None          # TGCAugment: the num_bins gains
     clahe: tuple = None        # CLAHE: (clip, (gx, gy))
+    # device_augment="all": the float64 fields the host drew, (h, w) ndarrays.  Left out of ==
+    # (an ndarray has no truth value); without them the record compares and pickles as before.
+    # ElasticDeform, first in the chain: (alpha, the Gaussian taps, rx, ry)
+    elastic: tuple = dataclasses.field(default=None, compare=False)
+    # SpeckleNoise, between AdjustBrightness and TGCAugment: the noise field
+    speckle: np.ndarray = dataclasses.field(default=None, compare=False)
 
     def geometric(self):
         return self.flip_h or self.flip_v or self.angle is not None
 
+    def elastic_params(self):
+        """unet_elastic_params of the elastic draw."""
+        alpha, taps = self.elastic[:2]
+        p = _lib.ElasticParams()
+        if len(taps) > 31:
+            raise _lib.HipError(f"elastic blur of {len(taps)} taps: UNET_ERR_INVALID (31)")
+        p.ksize, p.alpha = len(taps), float(alpha)
+        p.k[:len(taps)] = [float(k) for k in taps]
+        return p
+
     def params(self, h, w, is_mask):
         """unet_aug_params of an (h, w) plane, or None when the launch would copy (the mask
         takes the geometry only)."""
-        point = not is_mask and (self.brightness is not None or self.tgc is not None)
+        point = not is_mask and (self.brightness is not None or self.tgc is not None or
+                                 self.speckle is not None)
         if not (self.geometric() or point):
             return None
         p = _lib.AugParams()
@@ -151,15 +176,41 @@ def _host_plane(a):
     return a
 
 
+def _field(a, h, w):
+    """An (h, w) float64 field of a record, C-contiguous."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != (h, w):
+        raise ValueError(f"a field of shape {a.shape} for a {(h, w)} plane")
+    return a
+
+
 def apply_augment_host(plane, record, is_mask=False):
     """The device chain of ``record`` on one (H, W) uint8 plane through the host hooks
-    (unet_augment_u8_host, unet_clahe_u8_host: the kernels' own source compiled for the host).
-    Keeps the plane's ``resample`` tag."""
+    (unet_elastic_u8_host, unet_augment_u8_host / unet_augment_noise_u8_host,
+    unet_clahe_u8_host: the kernels' own source compiled for the host).  Keeps the plane's
+    ``resample`` tag."""
     lib = _lib.load()
     src = _host_plane(plane)
     h, w = src.shape
+    if record.elastic is not None:
+        rx, ry = (_field(f, h, w) for f in record.elastic[2:])
+        dst = np.empty_like(src)
+        s, d = ctypes.c_void_p(src.ctypes.data), ctypes.c_void_p(dst.ctypes.data)
+        _lib.check(lib.unet_elastic_u8_host(None if is_mask else s, s if is_mask else None, h, w,
+                                            None if is_mask else d, d if is_mask else None,
+                                            rx.ctypes.data, ry.ctypes.data,
+                                            ctypes.byref(record.elastic_params())),
+                   None, "unet_elastic_u8_host")
+        src = dst
     p = record.params(h, w, is_mask)
-    if p is not None:
+    if p is not None and not is_mask and record.speckle is not None:
+        noise = _field(record.speckle, h, w)
+        dst = np.empty_like(src)
+        _lib.check(lib.unet_augment_noise_u8_host(src.ctypes.data, h, w, dst.ctypes.data,
+                                                  ctypes.byref(p), noise.ctypes.data),
+                   None, "unet_augment_noise_u8_host")
+        src = dst
+    elif p is not None:
         dst = np.empty_like(src)
         _lib.check(lib.unet_augment_u8_host(src.ctypes.data, h, w, dst.ctypes.data,
                                             ctypes.byref(p)), None, "unet_augment_u8_host")
@@ -204,19 +255,50 @@ class GpuResizeToTensor:
         return t.to(self.device, non_blocking=True).contiguous()
 
     def _scratch(self, k, h, w):
-        """Intermediate plane k (0 / 1) of the reused device buffer."""
+        """Intermediate plane k of the reused device buffer: 0 / 1 the point and CLAHE launches,
+        2 / 3 the elastic image / mask."""
         n = h * w
         if self._u8 is None or self._u8.shape[1] < n:
-            self._u8 = torch.empty((2, n), dtype=torch.uint8, device=self.device)
+            self._u8 = torch.empty((4, n), dtype=torch.uint8, device=self.device)
         return self._u8[k, :n].view(h, w)
 
-    def augment(self, t, rec, is_mask):
-        """The recorded augmentations of one (H, W) uint8 device plane: flip + rotate (+
-        brightness + TGC for an image) in one launch, then CLAHE if drawn.  Returns a view of
-        the reused buffer (valid until the next call) or ``t`` itself when nothing applies."""
+    def _upload_field(self, a, h, w):
+        """An (H, W) float64 field of a record, on the device (stream-ordered like the planes:
+        the caching allocator reuses the memory only behind the launches that read it)."""
+        return torch.from_numpy(_field(a, h, w)).to(self.device, non_blocking=True)
+
+    def elastic(self, ti, tm, rec):
+        """The recorded ElasticDeform of an image and / or its mask ((H, W) uint8 device planes,
+        either may be None) under the one map, in one call.  Returns views of the reused buffer
+        (valid until the next elastic call)."""
+        h, w = (ti if ti is not None else tm).shape
+        rx, ry = (self._upload_field(f, h, w) for f in rec.elastic[2:])
+        di = None if ti is None else self._scratch(2, h, w)
+        dm = None if tm is None else self._scratch(3, h, w)
+        _lib.check(self.rt.lib.unet_elastic_u8(
+            self.rt.ctx, _lib.ptr(ti), _lib.ptr(tm), h, w, _lib.ptr(di), _lib.ptr(dm), _lib.ptr(rx),
+            _lib.ptr(ry), ctypes.byref(rec.elastic_params()), _lib.stream_ptr(self.device)),
+            self.rt.ctx, "unet_elastic_u8")
+        return di, dm
+
+    def augment(self, t, rec, is_mask, elastic_done=False):
+        """The recorded augmentations of one (H, W) uint8 device plane: ElasticDeform if drawn
+        (unless ``elastic_done``: the pair went through ``elastic`` together), flip + rotate (+
+        brightness + speckle + TGC for an image) in one launch, then CLAHE if drawn.  Returns a
+        view of the reused buffer (valid until the next call) or ``t`` itself when nothing
+        applies."""
         h, w = t.shape
+        if rec.elastic is not None and not elastic_done:
+            t = self.elastic(None, t, rec)[1] if is_mask else self.elastic(t, None, rec)[0]
         p = rec.params(h, w, is_mask)
-        if p is not None:
+        if p is not None and not is_mask and rec.speckle is not None:
+            d = self._scratch(0, h, w)
+            noise = self._upload_field(rec.speckle, h, w)
+            _lib.check(self.rt.lib.unet_augment_noise_u8(
+                self.rt.ctx, _lib.ptr(t), h, w, _lib.ptr(d), ctypes.byref(p), _lib.ptr(noise),
+                _lib.stream_ptr(self.device)), self.rt.ctx, "unet_augment_noise_u8")
+            t = d
+        elif p is not None:
             d = self._scratch(0, h, w)
             _lib.check(self.rt.lib.unet_augment_u8(
                 self.rt.ctx, _lib.ptr(t), h, w, _lib.ptr(d), ctypes.byref(p),
@@ -231,12 +313,12 @@ class GpuResizeToTensor:
             t = d
         return t
 
-    def resize(self, img, out=None, aug=None, is_mask=False):
+    def resize(self, img, out=None, aug=None, is_mask=False, elastic_done=False):
         """One HxW uint8 image -> (oh, ow) fp32 in [0, 1] on the device."""
         nearest = getattr(img, "resample", "bilinear") == "nearest"
         t = self._upload(img)
         if aug is not None:
-            t = self.augment(t, aug, is_mask)
+            t = self.augment(t, aug, is_mask, elastic_done)
         h, w = t.shape
         if out is None:
             out = torch.empty((self.oh, self.ow), dtype=torch.float32, device=self.device)
@@ -257,11 +339,18 @@ class GpuResizeToTensor:
         elif len(aug) != n:
             raise ValueError(f"{len(aug)} augmentation records for {n} images")
         x = torch.empty((n, 1, self.oh, self.ow), dtype=torch.float32, device=self.device)
+        t = None if masks is None else torch.empty_like(x)
+        paired = [t is not None and r is not None and r.elastic is not None for r in aug]
         for i, im in enumerate(images):
-            self.resize(im, x[i, 0], aug[i])
+            if paired[i]:  # one elastic call deforms the image and its mask under the one map
+                di, dm = self.elastic(self._upload(im), self._upload(masks[i]), aug[i])
+                self.resize(di, x[i, 0], aug[i], elastic_done=True)
+                self.resize(dm, t[i, 0], aug[i], is_mask=True, elastic_done=True)
+            else:
+                self.resize(im, x[i, 0], aug[i])
         if masks is None:
             return x
-        t = torch.empty_like(x)
         for i, m in enumerate(masks):
-            self.resize(m, t[i, 0], aug[i], is_mask=True)
+            if not paired[i]:
+                self.resize(m, t[i, 0], aug[i], is_mask=True)
         return x, t

@@ -153,16 +153,26 @@ class ElasticDeform:
     def __init__(self, alpha=(20, 40), sigma=(6, 10), p=0.3):
         self.alpha, self.sigma, self.p = alpha, sigma, p
 
-    def __call__(self, img, mask):
+    def draw(self, h, w):
+        """(alpha, sigma, rx, ry) of an h x w sample -- rx, ry the uniform float64 fields the two
+        displacement maps are blurred from -- or None when the augmentation is not applied."""
         if random.random() > self.p:
+            return None
+        alpha = random.uniform(*self.alpha)
+        sigma = random.uniform(*self.sigma)
+        rx = np.random.rand(h, w)
+        return alpha, sigma, rx, np.random.rand(h, w)
+
+    def __call__(self, img, mask):
+        d = self.draw(img.size[1], img.size[0])
+        if d is None:
             return img, mask
+        alpha, sigma, rx, ry = d
         img_np = np.array(img)
         mask_np = np.array(mask)
         h, w = img_np.shape[:2]
-        alpha = random.uniform(*self.alpha)
-        sigma = random.uniform(*self.sigma)
-        dx = gaussian_blur(np.random.rand(h, w) * 2 - 1, 17, sigma) * alpha
-        dy = gaussian_blur(np.random.rand(h, w) * 2 - 1, 17, sigma) * alpha
+        dx = gaussian_blur(rx * 2 - 1, 17, sigma) * alpha
+        dy = gaussian_blur(ry * 2 - 1, 17, sigma) * alpha
         x, y = np.meshgrid(np.arange(w), np.arange(h))
         map_x = (x + dx).astype(np.float32)
         map_y = (y + dy).astype(np.float32)
@@ -181,11 +191,19 @@ class SpeckleNoise:
     def __init__(self, sigma=(0.05, 0.15), p=0.5):
         self.sigma, self.p = sigma, p
 
-    def __call__(self, img, mask):
+    def draw(self, shape):
+        """The float64 noise field of a sample whose array has ``shape``, or None when the
+        augmentation is not applied."""
         if random.random() > self.p:
+            return None
+        return np.random.normal(0, random.uniform(*self.sigma), shape)
+
+    def __call__(self, img, mask):
+        bands = len(img.getbands())  # np.array(img).shape without converting the image
+        noise = self.draw((img.size[1], img.size[0]) + ((bands,) if bands > 1 else ()))
+        if noise is None:
             return img, mask
         img_np = np.array(img).astype(np.float32) / 255.
-        noise = np.random.normal(0, random.uniform(*self.sigma), img_np.shape)
         img_np = img_np + img_np * noise
         img_np = np.clip(img_np * 255., 0, 255).astype(np.uint8)
         return Image.fromarray(img_np), mask
@@ -355,6 +373,11 @@ class ToTensor:
 
 
 DEVICE_AUGMENTS = (Flip, Rotate, AdjustBrightness, TGCAugment, CLAHE)
+# device_augment="all": the whole chain; ElasticDeform and SpeckleNoise send their float64
+# fields with the record
+ALL_DEVICE_AUGMENTS = (ElasticDeform, Flip, Rotate, AdjustBrightness, SpeckleNoise, TGCAugment,
+                       CLAHE)
+ELASTIC_KSIZE = 17  # ElasticDeform's GaussianBlur window (:27-28)
 
 
 class RecordAugment:
@@ -365,19 +388,39 @@ class RecordAugment:
     (unet_hip.data.AugRecord) for the device to apply (unet_hip.GpuResizeToTensor).
 
     The device applies Flip -> Rotate -> AdjustBrightness -> TGCAugment -> CLAHE, so the run
-    must hold at most one of each, in that order (as build_train_transform's chains do)."""
+    must hold at most one of each, in that order (as build_train_transform's chains do).
 
-    def __init__(self, transforms):
-        order = [DEVICE_AUGMENTS.index(type(t)) for t in transforms]  # ValueError: not capable
+    ``capable=ALL_DEVICE_AUGMENTS`` (device_augment="all") admits ElasticDeform in front and
+    SpeckleNoise after AdjustBrightness as well.  Their float64 fields are still drawn here,
+    from ``np.random`` with the host chain's calls, and travel with the record.  A pair the
+    device cannot reproduce exactly -- an image or mask that is not mode "L" (the host classes
+    convert "P" / "1" to "L" when they fire, which changes the later resize filter), or a side
+    below 9 (the blur's 8-pixel REFLECT_101 border has nothing to reflect) -- runs the host
+    transforms themselves, which make the same draws, and gets an empty record."""
+
+    def __init__(self, transforms, capable=DEVICE_AUGMENTS):
+        order = [capable.index(type(t)) for t in transforms]  # ValueError: not capable
         if order != sorted(set(order)):
-            raise ValueError("device augmentations: at most one of each, in the order Flip, "
-                             "Rotate, AdjustBrightness, TGCAugment, CLAHE")
+            raise ValueError("device augmentations: at most one of each, in the order " +
+                             ", ".join(c.__name__ for c in capable))
         self.transforms = list(transforms)
+        self.fields = any(isinstance(t, (ElasticDeform, SpeckleNoise)) for t in transforms)
 
-    def draw(self):
+    def draw(self, shape=None):
+        """``shape``: (h, w) of the sample, for the fields of ElasticDeform / SpeckleNoise."""
         from unet_hip.data import AugRecord
         rec = AugRecord()
         for t in self.transforms:
+            if isinstance(t, ElasticDeform):
+                d = t.draw(*shape)
+                if d is not None:
+                    alpha, sigma, rx, ry = d
+                    taps = tuple(float(k) for k in gaussian_kernel(ELASTIC_KSIZE, sigma))
+                    rec.elastic = (alpha, taps, rx, ry)
+                continue
+            if isinstance(t, SpeckleNoise):
+                rec.speckle = t.draw(tuple(shape))
+                continue
             d = t.draw()
             if isinstance(t, Flip):
                 rec.flip_h, rec.flip_v = d
@@ -393,7 +436,14 @@ class RecordAugment:
 
     def __call__(self, img, mask):
         from data.data_loader import DecodeU8
-        rec = self.draw()
+        if self.fields and (img.mode != "L" or mask.mode != "L" or mask.size != img.size or
+                            min(img.size) < ELASTIC_KSIZE // 2 + 1):
+            from unet_hip.data import AugRecord
+            for t in self.transforms:
+                img, mask = t(img, mask)
+            rec = AugRecord()
+        else:
+            rec = self.draw((img.size[1], img.size[0]))
         pi, pm = DecodeU8()(img, mask)
         pi.aug = pm.aug = rec
         return pi, pm
@@ -409,7 +459,11 @@ def build_train_transform(cfg, size=(512, 512), tail=None, device_augment=False)
     is split at its longest suffix of device-capable transforms (DEVICE_AUGMENTS).  The host
     prefix runs unchanged -- ElasticDeform alone with use_elastic; Flip ... SpeckleNoise with
     use_speckle, whose float64 noise field stays on the host -- and RecordAugment replaces the
-    suffix and the tail: it draws, decodes and hands the draws to the device."""
+    suffix and the tail: it draws, decodes and hands the draws to the device.
+
+    ``device_augment="all"``: the whole chain becomes one RecordAugment, ElasticDeform and
+    SpeckleNoise included (unet_elastic_u8 / unet_augment_noise_u8): the host keeps the draws,
+    the two fields among them, and touches no pixel."""
     tfs = []
     if getattr(cfg, "use_elastic", False):
         tfs.append(ElasticDeform(p=0.25))
@@ -423,6 +477,8 @@ def build_train_transform(cfg, size=(512, 512), tail=None, device_augment=False)
     if device_augment:
         if tail is not None:
             raise ValueError("device_augment decodes by itself: no tail")
+        if device_augment == "all":
+            return Compose([RecordAugment(tfs, ALL_DEVICE_AUGMENTS)])
         k = len(tfs)
         while k > 0 and isinstance(tfs[k - 1], DEVICE_AUGMENTS):
             k -= 1
