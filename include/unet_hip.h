@@ -26,6 +26,9 @@
  *                                                           distance_transform_edt(1 - gt), on the
  *                                                           device (no host round trip)
  *   unet_boundary_fwd / _bwd        models/loss.py:52-66   BoundaryLoss and its d/d(logits)
+ *   unet_surface_stats / _host      (new)                  per-sample surface-distance statistics
+ *                                                           of Trainer.test's masks (HD, HD95,
+ *                                                           ASSD: MedPy's hd / hd95 / assd)
  *   unet_adamw                      utils/trainer.py:41,92 AdamW.step (torch optim/adam.py
  *                                                           _single_tensor_adam, decoupled wd)
  *   unet_mask_counts                utils/trainer.py:217,236-242  sigmoid(x)>0.5 masks and
@@ -252,6 +255,32 @@ int unet_arena_changed(unet_ctx* ctx, const float* params, int64_t n);
  * calculate_iou).  mask (optional, may be null): uint8 (N,C,H,W). */
 int unet_mask_counts(unet_ctx* ctx, const float* logits, const float* targets, int64_t n,
                      uint8_t* mask, int64_t* counts, unet_stream_t stream);
+
+/* Surface-distance statistics of the masks unet_mask_counts reads (MedPy's hd, hd95 and assd at
+ * connectivity 1, in pixels; csrc/surf.h).  Per sample n, with P = sigmoid(logits[n, 0]) > 0.5
+ * and G = ((int)targets[n, 0] == 1) (channels above 0 are not read):
+ *   border(A)  the foreground pixels of A with a 4-neighbour that is background or outside the
+ *              image (A & ~binary_erosion(A), border_value 0);
+ *   d_PG       the squared Euclidean distances, exact in int32, from each pixel of border(P) to
+ *              the nearest pixel of border(G); d_GP likewise from border(G) to border(P);
+ *   out_i64[6 n ..] = {defined, n_PG, n_GP, max_d2, d2_lo, d2_hi}: the sizes of d_PG and d_GP,
+ *              the largest squared distance of both, and the order statistics
+ *              floor(0.95 (n - 1)) and ceil(0.95 (n - 1)) of the n = n_PG + n_GP squared
+ *              distances of both (the two values numpy.percentile(.., 95) interpolates between),
+ *              selected exactly by a radix select;
+ *   out_f64[2 n ..] = {sum_PG, sum_GP}: the float64 sums of sqrt(d2) over d_PG and d_GP.
+ * So HD = sqrt(max_d2), HD95 = lerp(sqrt(d2_lo), sqrt(d2_hi), frac(0.95 (n - 1))) and
+ * ASSD = (sum_PG / n_PG + sum_GP / n_GP) / 2.  A sample whose P or G is empty is undefined:
+ * defined = 0 and every other field 0.  Both outputs are device memory; all work is enqueued on
+ * `stream` with no host synchronisation, every sum in a fixed order (two runs agree bit for
+ * bit); the scratch is owned by the context and grown on demand (one stream per context, or
+ * ordered streams).  max(H, W) > 2048 is UNET_ERR_SHAPE, a null pointer UNET_ERR_INVALID.
+ * unet_surface_stats_host is the HOST twin (host pointers, same source); its float64 sums run
+ * over the pixels in raster order. */
+int unet_surface_stats(unet_ctx* ctx, const float* logits, const float* targets, int N, int C,
+                       int H, int W, int64_t* out_i64, double* out_f64, unet_stream_t stream);
+int unet_surface_stats_host(const float* logits, const float* targets, int N, int C, int H, int W,
+                            int64_t* out_i64, double* out_f64);
 
 /* Gradient buckets for data-parallel overlap.  Bucket b covers grads[offset, offset+len)
  * and is complete once the event recorded by unet_backward for it has fired; buckets

@@ -36,14 +36,16 @@ EDT_HD bool edt_site(float t) { return t >= 1.f && t < 2.f; }
 // One column of one sample: t / g2 point at row 0 of the column, consecutive rows `stride`
 // elements apart.  Writes g^2 (g = rows to the nearest site of the column, EDT_INF if none)
 // and returns whether the column holds a site.  Both sweeps load EDT_UNROLL rows before they
-// walk the dependent chain over them, so the loads of a batch are in flight together.
+// walk the dependent chain over them, so the loads of a batch are in flight together.  T is
+// float (the BoundaryLoss targets) or uint8_t (the 0 / 1 border planes of surf.h: 1 is a site).
 constexpr int EDT_UNROLL = 8;
-EDT_HD bool edt_column(const float* __restrict__ t, int* __restrict__ g2, int H, int64_t stride) {
+template <typename T>
+EDT_HD bool edt_column(const T* __restrict__ t, int* __restrict__ g2, int H, int64_t stride) {
     int d = EDT_INF;
     for (int i0 = 0; i0 < H; i0 += EDT_UNROLL) {  // down: distance to the nearest site above
         float v[EDT_UNROLL];
 #pragma unroll
-        for (int u = 0; u < EDT_UNROLL; ++u) v[u] = i0 + u < H ? t[(i0 + u) * stride] : 0.f;
+        for (int u = 0; u < EDT_UNROLL; ++u) v[u] = i0 + u < H ? (float)t[(i0 + u) * stride] : 0.f;
 #pragma unroll
         for (int u = 0; u < EDT_UNROLL; ++u)
             if (i0 + u < H) {

@@ -134,6 +134,14 @@ int k_boundary_fwd(const float* x, const float* t, const float* dist, int N, int
                    float* part, double* sum, float* loss, hipStream_t s);
 int k_boundary_bwd(const float* x, const float* t, const float* dist, int N, int C, int64_t hw,
                    const float* w, float* dx, hipStream_t s);
+// Surface-distance statistics (kernels_surf.hip; definition and rules in surf.h).  scratch holds
+// surf_scratch_bytes(N, H, W); out_i64 6 and out_f64 2 values per sample (unet_surface_stats)
+size_t surf_scratch_bytes(int N, int H, int W);
+int k_surface_stats(const float* x, const float* t, int N, int C, int H, int W, void* scratch,
+                    int64_t* out_i64, double* out_f64, hipStream_t s);
+// border: 2 H W bytes, d2: 2 H W ints
+void surface_stats_host(const float* x, const float* t, int N, int C, int H, int W, uint8_t* border,
+                        int* d2, int64_t* out_i64, double* out_f64);
 // Training augmentations of uint8 planes (kernels_aug.hip; algorithms and rules in aug.h)
 struct ClaheGeom;
 int aug_params_check(const unet_aug_params* p, int h, int w);

@@ -6,6 +6,7 @@
 // reductions (no float atomics), so two runs of the same inputs are bit-identical.
 // Layout everywhere: NHWC, channel stride `ld`, channel offset `off` (concat slices).
 #include "kernels_misc.h"
+#include "surf.h"  // surf_pred / surf_target_u8: the mask readout
 #include "gemm_common.h"  // Pix, decode, pix_advance (and x3_split.h)
 
 namespace {
@@ -1808,9 +1809,9 @@ __global__ void mask_counts_kernel(const float* __restrict__ x, const float* __r
     unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
-        const bool pr = sigmoidf_(x[i]) > 0.5f;
+        const bool pr = surf_pred(x[i]);  // surf.h: the surface metrics read the same masks
         const float tv = t[i];
-        const uint8_t tu = (uint8_t)(int)tv;  // numpy astype(uint8) truncation of {0,1} floats
+        const uint8_t tu = surf_target_u8(tv);
         const bool pos = tu == 1, neg = tu == 0;
         if (mask) mask[i] = pr ? 1 : 0;
         c[0] += pr && pos;

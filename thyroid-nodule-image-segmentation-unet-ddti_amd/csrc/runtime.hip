@@ -317,6 +317,10 @@ struct unet_ctx {
     // ElasticDeform scratch (unet_elastic_u8: the row pass of both fields), grown the same way
     void* escr = nullptr;
     size_t escr_bytes = 0;
+    // surface-metric scratch (unet_surface_stats: border planes, squared distances, gather
+    // partials), grown the same way
+    void* sscr = nullptr;
+    size_t sscr_bytes = 0;
     const float* pp_src = nullptr;
     bool pp_ok = false;
     uint64_t pp_gen = 0;
@@ -2524,7 +2528,7 @@ int unet_destroy(unet_ctx* c) {
     if (!c) return UNET_ERR_INVALID;
     for (auto e : c->bucket_ev) (void)hipEventDestroy(e);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->pp || c->pp3 || c->lpart || c->bscr || c->ascr || c->escr) {
+    if (c->pp || c->pp3 || c->lpart || c->bscr || c->ascr || c->escr || c->sscr) {
         (void)hipSetDevice(c->device);
         if (c->pp) (void)hipFree(c->pp);
         if (c->pp3) (void)hipFree(c->pp3);
@@ -2532,6 +2536,7 @@ int unet_destroy(unet_ctx* c) {
         if (c->bscr) (void)hipFree(c->bscr);
         if (c->ascr) (void)hipFree(c->ascr);
         if (c->escr) (void)hipFree(c->escr);
+        if (c->sscr) (void)hipFree(c->sscr);
         for (void* p : c->bscr_old) (void)hipFree(p);
     }
     delete c;
@@ -2763,6 +2768,43 @@ int unet_edt_host(const float* targets, int N, int C, int H, int W, float* dist)
     try {
         std::vector<int> g2((size_t)N * H * W);
         edt_host(targets, N, C, H, W, g2.data(), dist);
+        return UNET_OK;
+    } catch (const std::bad_alloc&) {
+        return UNET_ERR_NOMEM;
+    } catch (...) {
+        return UNET_ERR_INTERNAL;
+    }
+}
+
+static bool surf_shape_ok(int N, int C, int H, int W) {
+    return N >= 1 && C >= 1 && H >= 1 && W >= 1 && H <= EDT_MAX_SIDE && W <= EDT_MAX_SIDE &&
+           2 * (int64_t)N * std::max(H, W) < (int64_t)1 << 31 &&
+           (int64_t)N * H * W < (int64_t)1 << 36;
+}
+
+int unet_surface_stats(unet_ctx* c, const float* logits, const float* targets, int N, int C, int H,
+                       int W, int64_t* out_i64, double* out_f64, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !logits || !targets || !out_i64 || !out_f64) return UNET_ERR_INVALID;
+    if (!surf_shape_ok(N, C, H, W))
+        return fail(c, UNET_ERR_SHAPE, "surface_stats: N, C, H, W >= 1 and max(H, W) <= %d",
+                    EDT_MAX_SIDE);
+    if (int r = grow_scratch(c, c->sscr, c->sscr_bytes, surf_scratch_bytes(N, H, W), "surface"))
+        return r;
+    int r = k_surface_stats(logits, targets, N, C, H, W, c->sscr, out_i64, out_f64,
+                            (hipStream_t)stream);
+    return r ? fail(c, UNET_ERR_HIP, "surface_stats launch %d", r) : UNET_OK;
+    ABI_CATCH(c)
+}
+
+int unet_surface_stats_host(const float* logits, const float* targets, int N, int C, int H, int W,
+                            int64_t* out_i64, double* out_f64) {
+    if (!logits || !targets || !out_i64 || !out_f64) return UNET_ERR_INVALID;
+    if (!surf_shape_ok(N, C, H, W)) return UNET_ERR_SHAPE;
+    try {
+        std::vector<uint8_t> border(2 * (size_t)H * W);
+        std::vector<int> d2(2 * (size_t)H * W);
+        surface_stats_host(logits, targets, N, C, H, W, border.data(), d2.data(), out_i64, out_f64);
         return UNET_OK;
     } catch (const std::bad_alloc&) {
         return UNET_ERR_NOMEM;

@@ -88,6 +88,9 @@ def get_parser(argv=None):
     p.add_argument("--mode", choices=["train", "test", "both"], default="test")
     p.add_argument("--image_size", type=int, default=512)
     p.add_argument("--synthetic", type=int, default=0, help="synthetic samples per split")
+    p.add_argument("--surface_metrics", action="store_true",
+                   help="test: also report HD95, HD and ASSD (pixels) of the predicted contours, "
+                        "computed on the GPU")
     return p.parse_args(argv)
 
 

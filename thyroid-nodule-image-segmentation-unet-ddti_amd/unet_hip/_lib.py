@@ -100,6 +100,10 @@ SIGNATURES = {
     "unet_get_option": (c_int, [c_void_p, c_char_p, P(c_int64)]),
     "unet_mask_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                  c_void_p]),
+    "unet_surface_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                   c_void_p, c_void_p, c_void_p]),
+    "unet_surface_stats_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                        c_void_p]),
     "unet_num_buckets": (c_int, [c_void_p, P(c_int)]),
     "unet_bucket_range": (c_int, [c_void_p, c_int, P(c_int64), P(c_int64)]),
     "unet_stream_wait_bucket": (c_int, [c_void_p, c_int, c_void_p]),

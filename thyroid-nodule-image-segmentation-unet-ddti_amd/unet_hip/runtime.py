@@ -210,6 +210,17 @@ class UNetRuntime:
                                        _lib.ptr(mask), _lib.ptr(counts), _lib.stream_ptr(logits.device))
         _lib.check(rc, self.ctx, "unet_mask_counts")
 
+    def surface_stats(self, logits, targets):
+        """Per-sample surface-distance statistics (unet_surface_stats): int64 (N, 6)
+        {defined, n_PG, n_GP, max_d2, d2_lo, d2_hi} and float64 (N, 2) {sum_PG, sum_GP}."""
+        N, C, H, W = logits.shape
+        oi = torch.empty((N, 6), dtype=torch.int64, device=logits.device)
+        of = torch.empty((N, 2), dtype=torch.float64, device=logits.device)
+        rc = self.lib.unet_surface_stats(self.ctx, _lib.ptr(logits), _lib.ptr(targets), N, C, H, W,
+                                         _lib.ptr(oi), _lib.ptr(of), _lib.stream_ptr(logits.device))
+        _lib.check(rc, self.ctx, "unet_surface_stats")
+        return oi, of
+
     def stream_wait_bucket(self, b, stream):
         rc = self.lib.unet_stream_wait_bucket(self.ctx, b, ctypes.c_void_p(stream.cuda_stream))
         _lib.check(rc, self.ctx, "unet_stream_wait_bucket")

@@ -26,6 +26,8 @@ What runs where (MI355X-first):
   loss and dlogits kernels, no host sync) and is only evaluated when its ratio != 0 (the
   reference evaluates it every step even at ratio 0; 0 * finite == 0, so skipping it changes
   no number).
+* ``test()`` with ``config.surface_metrics``: HD95, HD and ASSD of every test sample on the
+  device too (``unet_hip.surface_metrics``); five sums come back once, at the end.
 """
 import os
 import random
@@ -304,6 +306,9 @@ class Trainer:
         counts = torch.zeros(6, dtype=torch.int64, device=self.device)
         total = 0
         keep = []
+        surface = bool(getattr(self.config, "surface_metrics", False))
+        if surface:  # sums of hd95, hd, assd over the defined samples; defined, undefined
+            ssums = torch.zeros(5, dtype=torch.float64, device=self.device)
         for batch in tqdm(self.test_loader, desc="Testing Model", leave=True):
             if batch is None:  # empty DataParallel shard: nothing to count on this rank
                 keep.append(None)
@@ -314,6 +319,8 @@ class Trainer:
             logits = self.model(images)
             mask = torch.empty(logits.shape, dtype=torch.uint8, device=self.device)
             self.rt.mask_counts(logits, masks, counts, mask)
+            if surface:
+                ssums += self._surface_sums(logits, masks)
             total += images.size(0)
             keep.append((images.cpu(), masks.cpu(), mask.cpu()))
         if _distributed():
@@ -328,6 +335,18 @@ class Trainer:
         if self.rank0:
             print(msg)
         self.logger.info(msg)
+        if surface:
+            if _distributed():
+                dist.all_reduce(ssums)
+            hd95, hd, assd, k, u = ssums.tolist()  # the one transfer
+            k, u = int(k), int(u)
+            hd95, hd, assd = ((v / k if k else float("nan")) for v in (hd95, hd, assd))
+            smsg = (f"Surface Metrics — HD95={hd95:.4f}, HD={hd:.4f}, ASSD={assd:.4f} px "
+                    f"over {k} of {total} images ({u} undefined)")
+            if self.rank0:
+                print(smsg)
+            self.logger.info(smsg)
+            m.update(HD95=hd95, HD=hd, ASSD=assd, SurfaceDefined=k)
         if _distributed() and self._can_plot():
             # one set of PNGs over the whole test set, in the reference's sample order: batch
             # by batch, each batch's shards in rank order (DataParallel's gather order)
@@ -340,6 +359,16 @@ class Trainer:
         if keep and self.rank0:
             self._plot_contours(keep)
         return m
+
+    @staticmethod
+    def _surface_sums(logits, masks):
+        """float64[5] on the device: the batch's sums of the per-sample hd95, hd and assd over its
+        defined samples, then how many are defined and how many are not (P or G empty)."""
+        s = unet_hip.surface_metrics(logits, masks)
+        ok = s["defined"] != 0
+        zero = torch.zeros_like(s["hd"])
+        parts = [torch.where(ok, s[k], zero).sum() for k in ("hd95", "hd", "assd")]
+        return torch.stack(parts + [ok.sum().double(), (~ok).sum().double()])
 
     @staticmethod
     def _can_plot():
