@@ -29,6 +29,12 @@
  *   unet_surface_stats / _host      (new)                  per-sample surface-distance statistics
  *                                                           of Trainer.test's masks (HD, HD95,
  *                                                           ASSD: MedPy's hd / hd95 / assd)
+ *   unet_components / _host         (new)                  connected components of a mask, numbered
+ *                                                           as scipy.ndimage.label numbers them
+ *   unet_postprocess / _host        (new)                  drop small components, keep the largest,
+ *                                                           fill holes (scipy's binary_fill_holes)
+ *   unet_lesion_stats / _host       (new)                  per-sample component counts of prediction
+ *                                                           and target and how many of each are hit
  *   unet_adamw                      utils/trainer.py:41,92 AdamW.step (torch optim/adam.py
  *                                                           _single_tensor_adam, decoupled wd)
  *   unet_mask_counts                utils/trainer.py:217,236-242  sigmoid(x)>0.5 masks and
@@ -282,6 +288,56 @@ int unet_surface_stats(unet_ctx* ctx, const float* logits, const float* targets,
 int unet_surface_stats_host(const float* logits, const float* targets, int N, int C, int H, int W,
                             int64_t* out_i64, double* out_f64);
 
+/* Connected components of the masks unet_mask_counts reads, the post-processing built on them and
+ * lesion-level detection counts (csrc/cc.h; kernels in csrc/kernels_cc.hip).  All integer and
+ * exact: the device, the host twins and scipy agree bit for bit, whatever the order of the atomics.
+ * src is (N, C, H, W), channel 0 read, and `kind` selects its foreground:
+ *   0  uint8, nonzero (C = 1: a uint8[N, H, W] plane);
+ *   1  float logits, sigmoid(x) > 0.5 as unet_mask_counts forms it;
+ *   2  float targets, (int)t == 1.
+ * connectivity 1 is scipy's generate_binary_structure(2, 1) (4 neighbours), 2 is np.ones((3, 3))
+ * (8 neighbours).
+ *   unet_components   labels int32[N, H, W] = scipy.ndimage.label of each sample: 0 background,
+ *                     1..K components in raster order of their first pixel (label = 1 + the rank,
+ *                     among the sample's components, of the component's smallest linear index);
+ *                     count int32[N] = K.  Phases, one launch each: a tile pass (a 64-column tile
+ *                     per block in LDS, row runs by wave ballot, union-find with LDS atomicMin), a
+ *                     seam pass (lock-free union by smaller index across tile borders), a flatten
+ *                     pass (label = find, roots per row, areas) and a rank pass (raster rank of the
+ *                     roots, then the labels rewritten to 1..K).  No kernel waits for another block.
+ *   unet_postprocess  out uint8[N, H, W] in {0, 1}, out != src: of each sample's foreground,
+ *                     (1) the components with area >= min_area (min_area <= 1 keeps all), then
+ *                     (2) if keep_largest, the largest of them, on equal areas the lowest label
+ *                     (np.argmax(np.bincount(lab.ravel())[1:]) + 1; empty stays empty), then
+ *                     (3) if fill_holes, scipy.ndimage.binary_fill_holes (default structure: the
+ *                     background components, at connectivity 1, that do not touch the image
+ *                     border become foreground).  info int64[4 N] = {components before,
+ *                     components kept, foreground pixels after, pixels filled} per sample.
+ *   unet_lesion_stats out int64[4 N] = {n_pred, n_gt, gt_hit, pred_hit} per sample for the
+ *                     prediction `pred` (any kind) and the float targets (kind 2, same N, C, H, W):
+ *                     the component counts of both, the target components that hold a pixel of the
+ *                     prediction and the predicted components that hold a pixel of the target.
+ * A connectivity other than 1 or 2, an unknown kind, N, C, H or W < 1, H * W >= 2^31 or a null
+ * pointer is UNET_ERR_INVALID; a batch whose pixel count does not fit one launch (about 2^39) is
+ * UNET_ERR_SHAPE.  Outputs are device memory; all work is enqueued on `stream` with no host
+ * synchronisation; labels, areas and flags live in a context-owned scratch grown on demand (one
+ * stream per context, or ordered streams).  The _host functions are the HOST twins (host
+ * pointers, the same cc.h rules). */
+int unet_components(unet_ctx* ctx, const void* src, int kind, int N, int C, int H, int W,
+                    int connectivity, int32_t* labels, int32_t* count, unet_stream_t stream);
+int unet_components_host(const void* src, int kind, int N, int C, int H, int W, int connectivity,
+                         int32_t* labels, int32_t* count);
+int unet_postprocess(unet_ctx* ctx, const void* src, int kind, int N, int C, int H, int W,
+                     int connectivity, int keep_largest, int64_t min_area, int fill_holes,
+                     uint8_t* out, int64_t* info, unet_stream_t stream);
+int unet_postprocess_host(const void* src, int kind, int N, int C, int H, int W, int connectivity,
+                          int keep_largest, int64_t min_area, int fill_holes, uint8_t* out,
+                          int64_t* info);
+int unet_lesion_stats(unet_ctx* ctx, const void* pred, int kind, const float* targets, int N, int C,
+                      int H, int W, int connectivity, int64_t* out, unet_stream_t stream);
+int unet_lesion_stats_host(const void* pred, int kind, const float* targets, int N, int C, int H,
+                           int W, int connectivity, int64_t* out);
+
 /* Gradient buckets for data-parallel overlap.  Bucket b covers grads[offset, offset+len)
  * and is complete once the event recorded by unet_backward for it has fired; buckets
  * become ready in order 0, 1, ... (decoder first). */
@@ -411,6 +467,7 @@ int unet_clahe_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, double cl
  *   tile_n32 tile_convt64 tile_convt tile_convt_dgrad rg16 rg16_tile rg16_bn_k rg16_r3 rg16_n128
  *   rg16_n128_bn wg16 wg16_tile wg16_r3 convt16 wg16t xcd16 xcd_remap dz_in_wgrad x3 x3_tile
  *   x3_wtile x3_wblocks x3_n64 x3_r3 head_fuse pool_fuse x3_wwaves x3_wwaves1 tile_group
+ *   cc_tile
  * Set them between steps, not between a forward and its backward: the workspace plan and
  * which saved images exist depend on them (x3, convt16, the bf16 kernel choices, ...), so
  * unet_backward returns UNET_ERR_INVALID when any option differs from those of the training

@@ -183,3 +183,37 @@ int k_mask_counts(const float* x, const float* t, int64_t n, uint8_t* mask, int6
                   hipStream_t s);
 int k_nchw_to_nhwc(const float* x, int N, int C, int HW, float* y, hipStream_t s);
 int k_fill(float* p, int64_t n, float v, hipStream_t s);
+
+// Connected components, post-processing and lesion counts (kernels_cc.hip; rules in cc.h).  The
+// phases are separate launchers so that the context can time each one.  Plane q of a call lives
+// at L + q H W; `tile` picks the tile rows (cc_tile_rows: 0 = 16, 1 = 32, 2 = 64; 64 columns).
+struct CcScratch {
+    unsigned long long* best;  // N keys of the largest kept component
+    int *cnt, *kept, *rowcnt;  // planes component counts, N kept counts, planes H roots per row
+    size_t zero_bytes;         // the leading part every call zeroes
+    int *L, *area;             // planes H W labels; areas, or flags, or ranks of the roots
+    size_t bytes;
+};
+CcScratch cc_scratch(void* base, int N, int planes, int H, int W);
+bool cc_grid_ok(int planes, int H, int W);
+int cc_tile_rows(int tile);
+int k_cc_tile(const void* src, int kind, int64_t sample_stride, int planes, int H, int W, int conn,
+              int tile, int* L, int* area, hipStream_t s);
+int k_cc_seam(int* L, int planes, int H, int W, int conn, int tile, hipStream_t s);
+// area / rowcnt / cnt may be null (not wanted)
+int k_cc_flatten(int* L, int* area, int* rowcnt, int* cnt, int planes, int H, int W, hipStream_t s);
+int k_cc_rank(const int* L, int* rk, const int* rowcnt, int* count, int planes, int H, int W,
+              int* labels, hipStream_t s);
+int k_cc_select(const int* L, const int* area, int64_t min_area, int* kept, unsigned long long* best,
+                int N, int H, int W, hipStream_t s);
+int k_cc_write(const int* L, const int* area, int64_t min_area, int keep_largest, const int* cnt,
+               const int* kept, const unsigned long long* best, uint8_t* out, int64_t* info, int N, int H,
+               int W, hipStream_t s);
+int k_cc_fill(const int* L, int* flag, uint8_t* out, int64_t* info, int N, int H, int W, hipStream_t s);
+int k_cc_hits(const int* L, int* flag, int64_t* out, int N, int H, int W, hipStream_t s);
+void components_host(const void* src, int kind, int N, int C, int H, int W, int conn, int* labels,
+                     int* count);
+void postprocess_host(const void* src, int kind, int N, int C, int H, int W, int conn, int keep_largest,
+                      int64_t min_area, int fill_holes, uint8_t* out, int64_t* info);
+void lesion_stats_host(const void* pred, int kind, const float* targets, int N, int C, int H, int W,
+                       int conn, int64_t* out);

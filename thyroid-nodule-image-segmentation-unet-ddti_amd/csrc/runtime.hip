@@ -31,6 +31,7 @@
 
 #include "../../include/unet_hip.h"
 #include "aug.h"
+#include "cc.h"
 #include "edt.h"
 #include "kernels_misc.h"
 #include "x3_split.h"
@@ -173,6 +174,8 @@ struct Options {
     int tile_group = 1;        // (r06) row-GEMM tile order of the LDS-DMA kernels (rg16, x3): 1 = grouped
                                // where the N tiles are many (tile_group_auto), 0 = M-major (r05);
                                // bit-identical
+    int cc_tile = 1;           // connected components: tile rows (0 = 16, 1 = 32, 2 = 64; 64 columns);
+                               // same labels for every value (profiles/cc_time.txt)
 };
 struct OptionDesc {
     const char* name;
@@ -222,6 +225,7 @@ const OptionDesc OPTION_TABLE[] = {
     {"x3_wwaves", &Options::x3_wwaves},
     {"x3_wwaves1", &Options::x3_wwaves1},
     {"tile_group", &Options::tile_group},
+    {"cc_tile", &Options::cc_tile},
 };
 
 }  // namespace
@@ -321,6 +325,10 @@ struct unet_ctx {
     // partials), grown the same way
     void* sscr = nullptr;
     size_t sscr_bytes = 0;
+    // connected-component scratch (unet_components / _postprocess / _lesion_stats: labels, areas
+    // and flags, counts), grown the same way
+    void* cscr = nullptr;
+    size_t cscr_bytes = 0;
     const float* pp_src = nullptr;
     bool pp_ok = false;
     uint64_t pp_gen = 0;
@@ -2528,7 +2536,7 @@ int unet_destroy(unet_ctx* c) {
     if (!c) return UNET_ERR_INVALID;
     for (auto e : c->bucket_ev) (void)hipEventDestroy(e);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->pp || c->pp3 || c->lpart || c->bscr || c->ascr || c->escr || c->sscr) {
+    if (c->pp || c->pp3 || c->lpart || c->bscr || c->ascr || c->escr || c->sscr || c->cscr) {
         (void)hipSetDevice(c->device);
         if (c->pp) (void)hipFree(c->pp);
         if (c->pp3) (void)hipFree(c->pp3);
@@ -2537,6 +2545,7 @@ int unet_destroy(unet_ctx* c) {
         if (c->ascr) (void)hipFree(c->ascr);
         if (c->escr) (void)hipFree(c->escr);
         if (c->sscr) (void)hipFree(c->sscr);
+        if (c->cscr) (void)hipFree(c->cscr);
         for (void* p : c->bscr_old) (void)hipFree(p);
     }
     delete c;
@@ -2811,6 +2820,147 @@ int unet_surface_stats_host(const float* logits, const float* targets, int N, in
     } catch (...) {
         return UNET_ERR_INTERNAL;
     }
+}
+
+// ---- connected components, post-processing, lesion counts (kernels_cc.hip, cc.h) ----
+static const char* cc_args_error(int kind, int N, int C, int H, int W, int conn) {
+    if (conn != 1 && conn != 2) return "connectivity must be 1 or 2";
+    if (kind < 0 || kind > 2) return "kind must be 0 (uint8 mask), 1 (logits) or 2 (targets)";
+    if (N < 1 || C < 1 || H < 1 || W < 1) return "N, C, H, W >= 1";
+    if ((int64_t)H * W >= (int64_t)1 << 31) return "H * W must be below 2^31";
+    return nullptr;
+}
+
+// tile, seam and flatten of `planes` planes read from src (see k_cc_tile) into sc.L at plane q0
+static int cc_label(unet_ctx* c, Launcher& ln, const char* what, const void* src, int kind,
+                    int64_t sample_stride, int q0, int planes, int H, int W, int conn,
+                    const CcScratch& sc, bool areas, bool rows, bool counts) {
+    const int64_t hw = (int64_t)H * W;
+    const int tile = c->opt.cc_tile;
+    int* L = sc.L + q0 * hw;
+    int* area = sc.area + q0 * hw;
+    hipStream_t s = ln.s;
+    const std::string w = what;
+    if (int r = ln.run("cc/tile|" + w, 0, [&] { return k_cc_tile(src, kind, sample_stride, planes, H, W, conn, tile, L, area, s); }))
+        return r;
+    if (int r = ln.run("cc/seam|" + w, 0, [&] { return k_cc_seam(L, planes, H, W, conn, tile, s); })) return r;
+    return ln.run("cc/flatten|" + w, 0, [&] {
+        return k_cc_flatten(L, areas ? area : nullptr, rows ? sc.rowcnt + (int64_t)q0 * H : nullptr,
+                            counts ? sc.cnt + q0 : nullptr, planes, H, W, s);
+    });
+}
+
+static int cc_prepare(unet_ctx* c, const char* what, int N, int planes, int H, int W, hipStream_t s,
+                      CcScratch& sc) {
+    if (!cc_grid_ok(planes, H, W)) return fail(c, UNET_ERR_SHAPE, "%s: batch too large for one launch", what);
+    const size_t need = cc_scratch(nullptr, N, planes, H, W).bytes;
+    if (int r = grow_scratch(c, c->cscr, c->cscr_bytes, need, "components")) return r;
+    sc = cc_scratch(c->cscr, N, planes, H, W);
+    if (hipMemsetAsync(c->cscr, 0, sc.zero_bytes, s) != hipSuccess) return fail(c, UNET_ERR_HIP, "%s: memset", what);
+    return UNET_OK;
+}
+
+int unet_components(unet_ctx* c, const void* src, int kind, int N, int C, int H, int W,
+                    int connectivity, int32_t* labels, int32_t* count, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !src || !labels || !count) return UNET_ERR_INVALID;
+    if (const char* e = cc_args_error(kind, N, C, H, W, connectivity))
+        return fail(c, UNET_ERR_INVALID, "components: %s", e);
+    hipStream_t s = (hipStream_t)stream;
+    CcScratch sc;
+    if (int r = cc_prepare(c, "components", N, N, H, W, s, sc)) return r;
+    Launcher ln{c, s};
+    const int64_t hw = (int64_t)H * W;
+    if (int r = cc_label(c, ln, "components", src, kind, C * hw, 0, N, H, W, connectivity, sc, false, true, false))
+        return r;
+    return ln.run("cc/rank|components", 0,
+                  [&] { return k_cc_rank(sc.L, sc.area, sc.rowcnt, count, N, H, W, labels, s); });
+    ABI_CATCH(c)
+}
+
+int unet_postprocess(unet_ctx* c, const void* src, int kind, int N, int C, int H, int W,
+                     int connectivity, int keep_largest, int64_t min_area, int fill_holes,
+                     uint8_t* out, int64_t* info, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !src || !out || !info) return UNET_ERR_INVALID;
+    if (const char* e = cc_args_error(kind, N, C, H, W, connectivity))
+        return fail(c, UNET_ERR_INVALID, "postprocess: %s", e);
+    if ((const void*)out == src) return fail(c, UNET_ERR_INVALID, "postprocess: out must differ from src");
+    hipStream_t s = (hipStream_t)stream;
+    CcScratch sc;
+    if (int r = cc_prepare(c, "postprocess", N, N, H, W, s, sc)) return r;
+    if (hipMemsetAsync(info, 0, 4 * sizeof(int64_t) * (size_t)N, s) != hipSuccess)
+        return fail(c, UNET_ERR_HIP, "postprocess: memset");
+    Launcher ln{c, s};
+    const int64_t hw = (int64_t)H * W;
+    if (int r = cc_label(c, ln, "postprocess", src, kind, C * hw, 0, N, H, W, connectivity, sc, true, false, true))
+        return r;
+    if (int r = ln.run("cc/select|postprocess", 0,
+                       [&] { return k_cc_select(sc.L, sc.area, min_area, sc.kept, sc.best, N, H, W, s); }))
+        return r;
+    if (int r = ln.run("cc/write|postprocess", 0, [&] {
+            return k_cc_write(sc.L, sc.area, min_area, keep_largest, sc.cnt, sc.kept, sc.best, out, info, N, H, W, s);
+        }))
+        return r;
+    if (!fill_holes) return UNET_OK;
+    // the complement of `out` at connectivity 1; the tile pass leaves the flags (sc.area) zero
+    if (int r = cc_label(c, ln, "fill", out, CC_KIND_U8_ZERO, hw, 0, N, H, W, 1, sc, false, false, false))
+        return r;
+    return ln.run("cc/fill|fill", 0, [&] { return k_cc_fill(sc.L, sc.area, out, info, N, H, W, s); });
+    ABI_CATCH(c)
+}
+
+int unet_lesion_stats(unet_ctx* c, const void* pred, int kind, const float* targets, int N, int C,
+                      int H, int W, int connectivity, int64_t* out, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !pred || !targets || !out) return UNET_ERR_INVALID;
+    if (const char* e = cc_args_error(kind, N, C, H, W, connectivity))
+        return fail(c, UNET_ERR_INVALID, "lesion_stats: %s", e);
+    if (N > (1 << 29)) return fail(c, UNET_ERR_SHAPE, "lesion_stats: batch too large for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    CcScratch sc;
+    if (int r = cc_prepare(c, "lesion_stats", N, 2 * N, H, W, s, sc)) return r;
+    if (hipMemsetAsync(out, 0, 4 * sizeof(int64_t) * (size_t)N, s) != hipSuccess)
+        return fail(c, UNET_ERR_HIP, "lesion_stats: memset");
+    Launcher ln{c, s};
+    const int64_t hw = (int64_t)H * W;
+    if (int r = cc_label(c, ln, "pred", pred, kind, C * hw, 0, N, H, W, connectivity, sc, false, false, false))
+        return r;
+    if (int r = cc_label(c, ln, "targets", targets, CC_KIND_TARGETS, C * hw, N, N, H, W, connectivity, sc,
+                         false, false, false))
+        return r;
+    return ln.run("cc/hits|lesion", 0, [&] { return k_cc_hits(sc.L, sc.area, out, N, H, W, s); });
+    ABI_CATCH(c)
+}
+
+#define CC_HOST_BODY(call)                         \
+    try {                                          \
+        call;                                      \
+        return UNET_OK;                            \
+    } catch (const std::bad_alloc&) {              \
+        return UNET_ERR_NOMEM;                     \
+    } catch (...) {                                \
+        return UNET_ERR_INTERNAL;                  \
+    }
+
+int unet_components_host(const void* src, int kind, int N, int C, int H, int W, int connectivity,
+                         int32_t* labels, int32_t* count) {
+    if (!src || !labels || !count || cc_args_error(kind, N, C, H, W, connectivity)) return UNET_ERR_INVALID;
+    CC_HOST_BODY(components_host(src, kind, N, C, H, W, connectivity, labels, count))
+}
+
+int unet_postprocess_host(const void* src, int kind, int N, int C, int H, int W, int connectivity,
+                          int keep_largest, int64_t min_area, int fill_holes, uint8_t* out,
+                          int64_t* info) {
+    if (!src || !out || !info || (const void*)out == src || cc_args_error(kind, N, C, H, W, connectivity))
+        return UNET_ERR_INVALID;
+    CC_HOST_BODY(postprocess_host(src, kind, N, C, H, W, connectivity, keep_largest, min_area, fill_holes, out, info))
+}
+
+int unet_lesion_stats_host(const void* pred, int kind, const float* targets, int N, int C, int H, int W,
+                           int connectivity, int64_t* out) {
+    if (!pred || !targets || !out || cc_args_error(kind, N, C, H, W, connectivity)) return UNET_ERR_INVALID;
+    CC_HOST_BODY(lesion_stats_host(pred, kind, targets, N, C, H, W, connectivity, out))
 }
 
 int unet_boundary_fwd(unet_ctx* c, const float* logits, const float* targets, const float* dist,

@@ -3,6 +3,8 @@
 Same flags as the reference (``--dataset_path``, ``--checkpoint_path``, ``--bce_ratio`` ...
 ``--use_data_parallel``), with four additions (``--mfma {fp32,bf16}`` selects the GEMM
 arithmetic of ModUNet / ResUNet; ``--use_amp_autocast`` stays parsed and ignored):
+``--pp_largest`` / ``--pp_min_area`` / ``--pp_fill_holes`` / ``--pp_connectivity`` / ``--lesion_metrics``
+add connected-component post-processing and lesion-level detection to the test report;
 ``--model_type`` picks the network
 (``ResUNet``: models/mod.py:88-131, what the reference hard-codes at main.py:120-122;
 ``ModUNet``: models/mod.py:9-66; ``UNet``: models/model.py, the BASELINE network and the
@@ -91,6 +93,17 @@ def get_parser(argv=None):
     p.add_argument("--surface_metrics", action="store_true",
                    help="test: also report HD95, HD and ASSD (pixels) of the predicted contours, "
                         "computed on the GPU")
+    p.add_argument("--pp_largest", action="store_true",
+                   help="test: also report the metrics of the masks cleaned on the GPU; keep only "
+                        "the largest connected component")
+    p.add_argument("--pp_min_area", type=int, default=0, metavar="N",
+                   help="test: ... drop the components with fewer than N pixels")
+    p.add_argument("--pp_fill_holes", action="store_true", help="test: ... fill the holes")
+    p.add_argument("--pp_connectivity", type=int, default=1, choices=(1, 2),
+                   help="connectivity of the components (1: 4 neighbours, 2: 8)")
+    p.add_argument("--lesion_metrics", action="store_true",
+                   help="test: also report lesion-level recall, precision and false-positive "
+                        "components per image (of the cleaned masks when a --pp_* option is set)")
     return p.parse_args(argv)
 
 

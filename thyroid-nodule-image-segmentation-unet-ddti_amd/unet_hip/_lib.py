@@ -104,6 +104,18 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p]),
     "unet_surface_stats_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                         c_void_p]),
+    "unet_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                c_void_p, c_void_p]),
+    "unet_components_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                     c_void_p]),
+    "unet_postprocess": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "unet_postprocess_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int64, c_int, c_void_p, c_void_p]),
+    "unet_lesion_stats": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_int, c_void_p, c_void_p]),
+    "unet_lesion_stats_host": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                       c_void_p]),
     "unet_num_buckets": (c_int, [c_void_p, P(c_int)]),
     "unet_bucket_range": (c_int, [c_void_p, c_int, P(c_int64), P(c_int64)]),
     "unet_stream_wait_bucket": (c_int, [c_void_p, c_int, c_void_p]),

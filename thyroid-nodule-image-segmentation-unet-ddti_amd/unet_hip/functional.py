@@ -204,3 +204,127 @@ def surface_metrics_host(logits, targets):
                                              ctypes.c_void_p(of.data_ptr()))
     _lib.check(rc, None, "unet_surface_stats_host")
     return _surface_finalize(oi, of)
+
+
+# ---------------------------------------------------------------- connected components
+CC_KINDS = {"mask": 0, "logits": 1, "targets": 2}
+LESION_FIELDS = ("n_pred", "n_gt", "gt_hit", "pred_hit")
+POSTPROCESS_FIELDS = ("components", "kept", "pixels", "filled")
+
+
+def _cc_args(x, kind):
+    """x as a contiguous (N, C, H, W) tensor the library reads channel 0 of, and its kind code.
+    (H, W) is one sample, (N, H, W) a batch of planes; uint8 (or bool) is a mask, float logits
+    unless kind says "targets"."""
+    x = x.detach()
+    if x.dim() == 2:
+        x = x[None, None]
+    elif x.dim() == 3:
+        x = x[:, None]
+    elif x.dim() != 4:
+        raise ValueError(f"expected (H, W), (N, H, W) or (N, C, H, W), got {tuple(x.shape)}")
+    if kind is None:
+        kind = "logits" if x.dtype.is_floating_point else "mask"
+    if kind not in CC_KINDS:
+        raise ValueError(f"kind must be one of {sorted(CC_KINDS)} or None, got {kind!r}")
+    if kind == "mask":
+        if x.dtype == torch.bool:
+            x = x.to(torch.uint8)
+        if x.dtype != torch.uint8:
+            raise ValueError(f"a mask must be uint8 or bool, got {x.dtype}")
+    else:
+        x = x.float()
+    return x.contiguous(), CC_KINDS[kind]
+
+
+def _cc_host_call(name, *args):
+    import ctypes
+
+    from . import _lib
+    conv = [ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+    _lib.check(getattr(_lib.load(), name)(*conv), None, name)
+
+
+def _cc_cpu(x, what):
+    if x.device.type != "cpu":
+        raise ValueError(f"{what} takes CPU tensors")
+
+
+def connected_components(x, connectivity=1, kind=None):
+    """``scipy.ndimage.label`` of every sample of x on the device and the current stream (no host
+    synchronisation): (labels int32 (N, H, W), count int32 (N,)), 0 background and 1..count[n]
+    the components in raster order of their first pixel, bit for bit scipy's numbering.
+    connectivity 1 = 4 neighbours, 2 = 8.  x: a uint8 / bool mask (nonzero is foreground), float
+    logits (the mask ``Trainer.test`` counts, sigmoid(x) > 0.5) or, with kind="targets", float
+    targets ((int)t == 1); (H, W), (N, H, W) or (N, C, H, W), channel 0 read."""
+    rt = _boundary_runtime(x, "connected_components")
+    x, k = _cc_args(x, kind)
+    return rt.components(x, k, int(connectivity))
+
+
+def connected_components_host(x, connectivity=1, kind=None):
+    """``connected_components`` of a CPU tensor through the library's host twin."""
+    _cc_cpu(x, "connected_components_host")
+    x, k = _cc_args(x, kind)
+    N, C, H, W = x.shape
+    labels = torch.empty((N, H, W), dtype=torch.int32)
+    count = torch.empty(N, dtype=torch.int32)
+    _cc_host_call("unet_components_host", x, k, N, C, H, W, int(connectivity), labels, count)
+    return labels, count
+
+
+def postprocess_mask(x, keep_largest=False, min_area=0, fill_holes=False, connectivity=1, kind=None):
+    """Clean the masks of x (as ``connected_components`` reads them) on the device: drop the
+    components with fewer than min_area pixels, then keep only the largest one left (ties: the
+    first in raster order) if keep_largest, then fill holes as ``scipy.ndimage.binary_fill_holes``
+    does if fill_holes.  Returns (mask uint8 (N, H, W) in {0, 1}, info int64 (N, 4) =
+    {components before, components kept, foreground pixels after, pixels filled})."""
+    rt = _boundary_runtime(x, "postprocess_mask")
+    x, k = _cc_args(x, kind)
+    return rt.postprocess(x, k, int(connectivity), keep_largest, min_area, fill_holes)
+
+
+def postprocess_mask_host(x, keep_largest=False, min_area=0, fill_holes=False, connectivity=1, kind=None):
+    """``postprocess_mask`` of a CPU tensor through the library's host twin."""
+    _cc_cpu(x, "postprocess_mask_host")
+    x, k = _cc_args(x, kind)
+    N, C, H, W = x.shape
+    out = torch.empty((N, H, W), dtype=torch.uint8)
+    info = torch.empty((N, 4), dtype=torch.int64)
+    _cc_host_call("unet_postprocess_host", x, k, N, C, H, W, int(connectivity), int(bool(keep_largest)),
+                  int(min_area), int(bool(fill_holes)), out, info)
+    return out, info
+
+
+def _lesion_args(pred, targets, kind):
+    p, k = _cc_args(pred, kind)
+    t, _ = _cc_args(targets, "targets")
+    if p.shape[0] != t.shape[0] or p.shape[2:] != t.shape[2:]:
+        raise ValueError(f"pred {tuple(pred.shape)} and targets {tuple(targets.shape)} differ")
+    if p.shape[1] != t.shape[1]:  # one channel count for both: channel 0 of each
+        p, t = p[:, :1].contiguous(), t[:, :1].contiguous()
+    return p, k, t
+
+
+def lesion_metrics(pred, targets, connectivity=1, kind=None):
+    """Lesion-level detection counts per sample, on the device: a dict of int64 (N,) tensors
+    ``n_pred`` and ``n_gt`` (components of the prediction and of the targets), ``gt_hit`` (target
+    components holding a predicted pixel) and ``pred_hit`` (predicted components holding a target
+    pixel).  pred as in ``connected_components``; targets float, (int)t == 1 is foreground."""
+    rt = _boundary_runtime(pred, "lesion_metrics")
+    if targets.device != pred.device:
+        raise ValueError("pred and targets must be on one device")
+    p, k, t = _lesion_args(pred, targets, kind)
+    out = rt.lesion_stats(p, k, t, int(connectivity))
+    return {f: out[:, i] for i, f in enumerate(LESION_FIELDS)}
+
+
+def lesion_metrics_host(pred, targets, connectivity=1, kind=None):
+    """``lesion_metrics`` of CPU tensors through the library's host twin."""
+    _cc_cpu(pred, "lesion_metrics_host")
+    _cc_cpu(targets, "lesion_metrics_host")
+    p, k, t = _lesion_args(pred, targets, kind)
+    N, C, H, W = p.shape
+    out = torch.empty((N, 4), dtype=torch.int64)
+    _cc_host_call("unet_lesion_stats_host", p, k, t, N, C, H, W, int(connectivity), out)
+    return {f: out[:, i] for i, f in enumerate(LESION_FIELDS)}

@@ -221,6 +221,39 @@ class UNetRuntime:
         _lib.check(rc, self.ctx, "unet_surface_stats")
         return oi, of
 
+    def components(self, x, kind, connectivity=1):
+        """labels int32 (N, H, W) and count int32 (N,) of x (N, C, H, W), channel 0
+        (unet_components; kind 0 uint8 mask, 1 logits, 2 targets)."""
+        N, C, H, W = x.shape
+        labels = torch.empty((N, H, W), dtype=torch.int32, device=x.device)
+        count = torch.empty(N, dtype=torch.int32, device=x.device)
+        rc = self.lib.unet_components(self.ctx, _lib.ptr(x), kind, N, C, H, W, connectivity,
+                                      _lib.ptr(labels), _lib.ptr(count), _lib.stream_ptr(x.device))
+        _lib.check(rc, self.ctx, "unet_components")
+        return labels, count
+
+    def postprocess(self, x, kind, connectivity=1, keep_largest=False, min_area=0, fill_holes=False):
+        """mask uint8 (N, H, W) and info int64 (N, 4) {components before, components kept,
+        foreground pixels after, pixels filled} (unet_postprocess)."""
+        N, C, H, W = x.shape
+        out = torch.empty((N, H, W), dtype=torch.uint8, device=x.device)
+        info = torch.empty((N, 4), dtype=torch.int64, device=x.device)
+        rc = self.lib.unet_postprocess(self.ctx, _lib.ptr(x), kind, N, C, H, W, connectivity,
+                                       int(bool(keep_largest)), int(min_area), int(bool(fill_holes)),
+                                       _lib.ptr(out), _lib.ptr(info), _lib.stream_ptr(x.device))
+        _lib.check(rc, self.ctx, "unet_postprocess")
+        return out, info
+
+    def lesion_stats(self, pred, kind, targets, connectivity=1):
+        """int64 (N, 4) {n_pred, n_gt, gt_hit, pred_hit} (unet_lesion_stats); pred and targets
+        are both (N, C, H, W)."""
+        N, C, H, W = pred.shape
+        out = torch.empty((N, 4), dtype=torch.int64, device=pred.device)
+        rc = self.lib.unet_lesion_stats(self.ctx, _lib.ptr(pred), kind, _lib.ptr(targets), N, C, H, W,
+                                        connectivity, _lib.ptr(out), _lib.stream_ptr(pred.device))
+        _lib.check(rc, self.ctx, "unet_lesion_stats")
+        return out
+
     def stream_wait_bucket(self, b, stream):
         rc = self.lib.unet_stream_wait_bucket(self.ctx, b, ctypes.c_void_p(stream.cuda_stream))
         _lib.check(rc, self.ctx, "unet_stream_wait_bucket")

@@ -28,6 +28,11 @@ What runs where (MI355X-first):
   no number).
 * ``test()`` with ``config.surface_metrics``: HD95, HD and ASSD of every test sample on the
   device too (``unet_hip.surface_metrics``); five sums come back once, at the end.
+* ``test()`` with a ``config.pp_*`` option (``pp_largest``, ``pp_min_area``, ``pp_fill_holes``,
+  ``pp_connectivity``): every batch's mask is cleaned on the device (``unet_hip.postprocess_mask``:
+  connected components, keep-largest, small-island removal, hole filling) and a second block of
+  ``PP_*`` metrics is reported for the cleaned masks; ``config.lesion_metrics`` adds lesion-level
+  recall, precision and false-positive components per image (``unet_hip.lesion_metrics``).
 """
 import os
 import random
@@ -309,6 +314,18 @@ class Trainer:
         surface = bool(getattr(self.config, "surface_metrics", False))
         if surface:  # sums of hd95, hd, assd over the defined samples; defined, undefined
             ssums = torch.zeros(5, dtype=torch.float64, device=self.device)
+        cfg = self.config
+        pp = dict(keep_largest=bool(getattr(cfg, "pp_largest", False)),
+                  min_area=int(getattr(cfg, "pp_min_area", 0) or 0),
+                  fill_holes=bool(getattr(cfg, "pp_fill_holes", False)),
+                  connectivity=int(getattr(cfg, "pp_connectivity", 1) or 1))
+        post = pp["keep_largest"] or pp["min_area"] > 0 or pp["fill_holes"]
+        lesion = bool(getattr(cfg, "lesion_metrics", False))
+        if post:  # the same sums for the post-processed masks
+            pcounts = torch.zeros(6, dtype=torch.int64, device=self.device)
+            psums = torch.zeros(5, dtype=torch.float64, device=self.device)
+        if lesion:  # n_pred, n_gt, gt_hit, pred_hit over the test set
+            lsums = torch.zeros(4, dtype=torch.int64, device=self.device)
         for batch in tqdm(self.test_loader, desc="Testing Model", leave=True):
             if batch is None:  # empty DataParallel shard: nothing to count on this rank
                 keep.append(None)
@@ -321,6 +338,16 @@ class Trainer:
             self.rt.mask_counts(logits, masks, counts, mask)
             if surface:
                 ssums += self._surface_sums(logits, masks)
+            if post:
+                # the cleaned mask as +-1 logits: the existing readout and surface kernels count it
+                clean, _ = unet_hip.postprocess_mask(mask, **pp)
+                plog = clean[:, None].float() * 2 - 1
+                self.rt.mask_counts(plog, masks[:, :1].contiguous(), pcounts)
+                if surface:
+                    psums += self._surface_sums(plog, masks[:, :1].contiguous())
+            if lesion:
+                les = unet_hip.lesion_metrics(clean if post else mask, masks, pp["connectivity"])
+                lsums += torch.stack([les[k].sum() for k in unet_hip.functional.LESION_FIELDS])
             total += images.size(0)
             keep.append((images.cpu(), masks.cpu(), mask.cpu()))
         if _distributed():
@@ -347,6 +374,42 @@ class Trainer:
                 print(smsg)
             self.logger.info(smsg)
             m.update(HD95=hd95, HD=hd, ASSD=assd, SurfaceDefined=k)
+        if post:
+            pm = global_metrics_from_counts(self._reduce_counts(pcounts).tolist())
+            pmsg = (f"Post-processed (largest={int(pp['keep_largest'])}, min_area={pp['min_area']}, "
+                    f"fill_holes={int(pp['fill_holes'])}, connectivity={pp['connectivity']})\n"
+                    f"  TP={pm['TP']}, FP={pm['FP']}, FN={pm['FN']}, TN={pm['TN']}\n"
+                    f"  ACC={pm['ACC']:.4f}, Precision={pm['Precision']:.4f}, "
+                    f"Recall={pm['Recall']:.4f}, F1={pm['F1']:.4f}, IoU={pm['IoU']:.4f}")
+            m.update({"PP_" + k: v for k, v in pm.items()})
+            if surface:
+                if _distributed():
+                    dist.all_reduce(psums)
+                hd95, hd, assd, k, u = psums.tolist()
+                k, u = int(k), int(u)
+                hd95, hd, assd = ((v / k if k else float("nan")) for v in (hd95, hd, assd))
+                pmsg += (f"\n  HD95={hd95:.4f}, HD={hd:.4f}, ASSD={assd:.4f} px over {k} of {total} "
+                         f"images ({u} undefined)")
+                m.update(PP_HD95=hd95, PP_HD=hd, PP_ASSD=assd, PP_SurfaceDefined=k)
+            if self.rank0:
+                print(pmsg)
+            self.logger.info(pmsg)
+        if lesion:
+            if _distributed():
+                dist.all_reduce(lsums)
+            n_pred, n_gt, gt_hit, pred_hit = lsums.tolist()  # the one transfer
+            nan = float("nan")
+            rec = gt_hit / n_gt if n_gt else nan
+            prec = pred_hit / n_pred if n_pred else nan
+            fpc = (n_pred - pred_hit) / total if total else nan
+            lmsg = (f"Lesion Metrics ({'post-processed' if post else 'raw'} masks, connectivity "
+                    f"{pp['connectivity']}) — Recall={rec:.4f} ({gt_hit}/{n_gt}), Precision={prec:.4f} "
+                    f"({pred_hit}/{n_pred}), FP components/image={fpc:.4f}")
+            if self.rank0:
+                print(lmsg)
+            self.logger.info(lmsg)
+            m.update(LesionRecall=rec, LesionPrecision=prec, FPComponentsPerImage=fpc,
+                     PredComponents=n_pred, GTComponents=n_gt)
         if _distributed() and self._can_plot():
             # one set of PNGs over the whole test set, in the reference's sample order: batch
             # by batch, each batch's shards in rank order (DataParallel's gather order)
