@@ -297,28 +297,7 @@ def test_adamw_vs_torch():
     assert torch.max(torch.abs(pa - pb)).item() <= 1e-6
 
 
-class _IeeeSqrtAdamW(O.AdamWState):
-    """The oracle's AdamW (torch's CPU ops, op for op) with a correctly rounded sqrt: this
-    host's vectorised torch.sqrt is 1 ulp low on ~0.7 % of fp32 inputs (measured against
-    IEEE sqrt; a host-library property, not part of the algorithm)."""
-
-    def step(self, params, grads):
-        import math
-        self.step_count += 1
-        b1, b2 = self.betas
-        bc1 = 1 - b1 ** self.step_count
-        bc2 = 1 - b2 ** self.step_count
-        step_size = self.lr / bc1
-        bc2_sqrt = math.sqrt(bc2)
-        with torch.no_grad():
-            for k, p in params.items():
-                g = grads[k]
-                p.mul_(1 - self.lr * self.wd)
-                self.m[k].lerp_(g, 1 - b1)
-                self.v[k].mul_(b2).addcmul_(g, g, value=1 - b2)
-                sq = torch.from_numpy(np.sqrt(self.v[k].numpy()))
-                denom = (sq / bc2_sqrt).add_(self.eps)
-                p.addcdiv_(self.m[k], denom, value=-step_size)
+from adamw_ref import IeeeSqrtAdamW as _IeeeSqrtAdamW  # noqa: E402  (shared with test_gpu_adamw_edges.py)
 
 
 @pytest.mark.parametrize("lr,wd,betas", [(1e-5, 1e-2, (0.9, 0.999)), (1e-3, 1e-2, (0.9, 0.999)),
@@ -326,7 +305,9 @@ class _IeeeSqrtAdamW(O.AdamWState):
 def test_adamw_bitwise_vs_oracle(lr, wd, betas):
     """The native AdamW vs the oracle's (torch's _single_tensor_adam CPU ops, utils/
     trainer.py:41,92) from IDENTICAL p, g, m, v at every one of 4 steps, over a flat arena
-    of 2^20 + 3 floats (16-B-vectorised kernel on the aligned body).
+    of 2^20 + 3 floats (n % 4 != 0, so k_adamw runs the scalar adamw_kernel over the whole
+    arena; the 16-B-vectorised adamw4_kernel is held to the same assertions in
+    tests/test_gpu_adamw_edges.py).
 
     * exp_avg and exp_avg_sq: bit-identical on every element;
     * params: bit-identical to the oracle's op sequence with a correctly rounded sqrt
