@@ -35,6 +35,10 @@
  *                                                           fill holes (scipy's binary_fill_holes)
  *   unet_lesion_stats / _host       (new)                  per-sample component counts of prediction
  *                                                           and target and how many of each are hit
+ *   unet_tta_views / _host          (new)                  flip / rotation test-time augmentation:
+ *                                                           the dihedral views of a batch, view-major
+ *   unet_tta_merge / _host          (new)                  un-warp the per-view logits, average
+ *                                                           them, threshold; per-pixel view votes
  *   unet_adamw                      utils/trainer.py:41,92 AdamW.step (torch optim/adam.py
  *                                                           _single_tensor_adam, decoupled wd)
  *   unet_mask_counts                utils/trainer.py:217,236-242  sigmoid(x)>0.5 masks and
@@ -337,6 +341,40 @@ int unet_lesion_stats(unet_ctx* ctx, const void* pred, int kind, const float* ta
                       int H, int W, int connectivity, int64_t* out, unet_stream_t stream);
 int unet_lesion_stats_host(const void* pred, int kind, const float* targets, int N, int C, int H,
                            int W, int connectivity, int64_t* out);
+
+/* Flip / rotation test-time augmentation (csrc/tta.h; kernels in csrc/kernels_tta.hip).  View k in
+ * 0..7 has bits h = k & 1, v = (k >> 1) & 1, t = (k >> 2) & 1:
+ *   T_k(x): y = x;  if t: y = y.swapaxes(-1, -2);  if v: y = y[..., ::-1, :];  if h: y = y[..., ::-1]
+ * (0 identity, 1..3 the flips, 4 transpose, 5 and 6 the quarter turns, 7 anti-transpose: D4).  `views`
+ * is a bit mask (bit k), K = popcount(views), the views taken in ascending k; named sets of the
+ * Python level: hflip 0x03, flips 0x0F, d4 0xFF.
+ *   unet_tta_views  out (K N, C, H, W), view-major: out[q N + n] = T_{k_q}(x[n]).  A pure
+ *                   permutation, bit-exact.
+ *   unet_tta_merge  logits (K N, C, H, W) in the same order: the model's output for `out`.  Per
+ *                   output element (n, c, i, j), x_q = T_{k_q}^-1(logits[q N + n, c])[i, j] (the
+ *                   inverse undoes h, then v, then t), and
+ *                     mode 0 (logit): score = (x_0 + ... + x_{K-1}) / (float)K,
+ *                                     mask = 1 / (1 + expf(-score)) > 0.5f (unet_mask_counts' readout);
+ *                     mode 1 (prob):  score = (p_0 + ... + p_{K-1}) / (float)K with
+ *                                     p_q = 1.f / (1.f + expf(-x_q)), mask = score > 0.5f;
+ *                     votes = the number of views with 1 / (1 + expf(-x_q)) > 0.5f (0..K).
+ *                   The sum is a float32 sum in ascending q, each operation rounded on its own, the
+ *                   division the correctly rounded one: two runs, and in mode 0 the device and the
+ *                   host twin, agree bit for bit.  score float (N, C, H, W); mask and votes uint8
+ *                   (N, C, H, W), either may be null; no output may overlap logits.
+ * views == 0 or a bit above 7, a mode other than 0 / 1, N, C, H or W < 1, H * W >= 2^31, a null x /
+ * out / logits / score or an output overlapping logits is UNET_ERR_INVALID; a view with t when
+ * H != W, or K * N * C >= 2^31, is UNET_ERR_SHAPE.  A row length that is no multiple of 4 and
+ * pointers that are only 4-byte aligned are legal (a scalar path).  All work is enqueued on `stream`
+ * with no host synchronisation, no scratch and no atomics.  The _host functions are the HOST twins
+ * (host pointers, the same tta.h rules). */
+int unet_tta_views(unet_ctx* ctx, const float* x, int N, int C, int H, int W, uint32_t views,
+                   float* out, unet_stream_t stream);
+int unet_tta_views_host(const float* x, int N, int C, int H, int W, uint32_t views, float* out);
+int unet_tta_merge(unet_ctx* ctx, const float* logits, int N, int C, int H, int W, uint32_t views,
+                   int mode, float* score, uint8_t* mask, uint8_t* votes, unet_stream_t stream);
+int unet_tta_merge_host(const float* logits, int N, int C, int H, int W, uint32_t views, int mode,
+                        float* score, uint8_t* mask, uint8_t* votes);
 
 /* Gradient buckets for data-parallel overlap.  Bucket b covers grads[offset, offset+len)
  * and is complete once the event recorded by unet_backward for it has fired; buckets

@@ -217,3 +217,12 @@ void postprocess_host(const void* src, int kind, int N, int C, int H, int W, int
                       int64_t min_area, int fill_holes, uint8_t* out, int64_t* info);
 void lesion_stats_host(const void* pred, int kind, const float* targets, int N, int C, int H, int W,
                        int conn, int64_t* out);
+
+// Test-time augmentation (kernels_tta.hip; rules in tta.h): the views of x, view-major, and the
+// merge of the per-view logits.  The callers have checked the arguments (runtime.hip).
+int k_tta_views(const float* x, int N, int C, int H, int W, uint32_t views, float* out, hipStream_t s);
+int k_tta_merge(const float* logits, int N, int C, int H, int W, uint32_t views, int mode, float* score,
+                uint8_t* mask, uint8_t* votes, hipStream_t s);
+void tta_views_host(const float* x, int N, int C, int H, int W, uint32_t views, float* out);
+void tta_merge_host(const float* logits, int N, int C, int H, int W, uint32_t views, int mode, float* score,
+                    uint8_t* mask, uint8_t* votes);

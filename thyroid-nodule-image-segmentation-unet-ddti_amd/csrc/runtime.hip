@@ -34,6 +34,7 @@
 #include "cc.h"
 #include "edt.h"
 #include "kernels_misc.h"
+#include "tta.h"
 #include "x3_split.h"
 
 namespace {
@@ -2961,6 +2962,76 @@ int unet_lesion_stats_host(const void* pred, int kind, const float* targets, int
                            int connectivity, int64_t* out) {
     if (!pred || !targets || !out || cc_args_error(kind, N, C, H, W, connectivity)) return UNET_ERR_INVALID;
     CC_HOST_BODY(lesion_stats_host(pred, kind, targets, N, C, H, W, connectivity, out))
+}
+
+// ---- test-time augmentation (kernels_tta.hip, tta.h) ----
+// UNET_OK, or the error code with *msg set
+static int tta_args_error(int N, int C, int H, int W, uint32_t views, const char** msg) {
+    *msg = nullptr;
+    if (views == 0 || (views & ~TTA_ALL_VIEWS)) *msg = "views must be a non-empty mask of the bits 0..7";
+    else if (N < 1 || C < 1 || H < 1 || W < 1) *msg = "N, C, H, W >= 1";
+    else if ((int64_t)H * W >= (int64_t)1 << 31) *msg = "H * W must be below 2^31";
+    if (*msg) return UNET_ERR_INVALID;
+    if ((views & 0xF0u) && H != W) *msg = "a transposed view (k >= 4) needs H == W";
+    else if ((int64_t)tta_view_list(views).K * N * C >= (int64_t)1 << 31) *msg = "K * N * C must be below 2^31";
+    return *msg ? UNET_ERR_SHAPE : UNET_OK;
+}
+
+static bool tta_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + nb && y < x + na;
+}
+// does an output of the merge overlap its input?
+static bool tta_merge_aliases(const float* logits, int N, int C, int H, int W, uint32_t views, const float* score,
+                              const uint8_t* mask, const uint8_t* votes) {
+    const size_t n = (size_t)N * C * H * W, in = sizeof(float) * n * tta_view_list(views).K;
+    return tta_overlap(logits, in, score, sizeof(float) * n) || tta_overlap(logits, in, mask, n) ||
+           tta_overlap(logits, in, votes, n);
+}
+
+int unet_tta_views(unet_ctx* c, const float* x, int N, int C, int H, int W, uint32_t views, float* out,
+                   unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !x || !out) return UNET_ERR_INVALID;
+    const char* e;
+    if (int r = tta_args_error(N, C, H, W, views, &e)) return fail(c, r, "tta_views: %s", e);
+    Launcher ln{c, (hipStream_t)stream};
+    return ln.run("tta/views", 0, [&] { return k_tta_views(x, N, C, H, W, views, out, ln.s); });
+    ABI_CATCH(c)
+}
+
+int unet_tta_merge(unet_ctx* c, const float* logits, int N, int C, int H, int W, uint32_t views, int mode,
+                   float* score, uint8_t* mask, uint8_t* votes, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !logits || !score) return UNET_ERR_INVALID;
+    const char* e;
+    if (int r = tta_args_error(N, C, H, W, views, &e)) return fail(c, r, "tta_merge: %s", e);
+    if (mode != TTA_MODE_LOGIT && mode != TTA_MODE_PROB)
+        return fail(c, UNET_ERR_INVALID, "tta_merge: mode must be 0 (logit) or 1 (prob)");
+    if (tta_merge_aliases(logits, N, C, H, W, views, score, mask, votes))
+        return fail(c, UNET_ERR_INVALID, "tta_merge: an output overlaps logits");
+    Launcher ln{c, (hipStream_t)stream};
+    return ln.run("tta/merge", 0,
+                  [&] { return k_tta_merge(logits, N, C, H, W, views, mode, score, mask, votes, ln.s); });
+    ABI_CATCH(c)
+}
+
+int unet_tta_views_host(const float* x, int N, int C, int H, int W, uint32_t views, float* out) {
+    if (!x || !out) return UNET_ERR_INVALID;
+    const char* e;
+    if (int r = tta_args_error(N, C, H, W, views, &e)) return r;
+    CC_HOST_BODY(tta_views_host(x, N, C, H, W, views, out))
+}
+
+int unet_tta_merge_host(const float* logits, int N, int C, int H, int W, uint32_t views, int mode, float* score,
+                        uint8_t* mask, uint8_t* votes) {
+    if (!logits || !score) return UNET_ERR_INVALID;
+    const char* e;
+    if (int r = tta_args_error(N, C, H, W, views, &e)) return r;
+    if ((mode != TTA_MODE_LOGIT && mode != TTA_MODE_PROB) ||
+        tta_merge_aliases(logits, N, C, H, W, views, score, mask, votes))
+        return UNET_ERR_INVALID;
+    CC_HOST_BODY(tta_merge_host(logits, N, C, H, W, views, mode, score, mask, votes))
 }
 
 int unet_boundary_fwd(unet_ctx* c, const float* logits, const float* targets, const float* dist,

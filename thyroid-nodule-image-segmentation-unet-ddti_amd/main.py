@@ -5,6 +5,8 @@ Same flags as the reference (``--dataset_path``, ``--checkpoint_path``, ``--bce_
 arithmetic of ModUNet / ResUNet; ``--use_amp_autocast`` stays parsed and ignored):
 ``--pp_largest`` / ``--pp_min_area`` / ``--pp_fill_holes`` / ``--pp_connectivity`` / ``--lesion_metrics``
 add connected-component post-processing and lesion-level detection to the test report;
+``--tta {none,hflip,flips,d4}`` / ``--tta_merge {prob,logit}`` add flip / rotation test-time
+augmentation to it (a ``TTA`` block after the unchanged raw one);
 ``--model_type`` picks the network
 (``ResUNet``: models/mod.py:88-131, what the reference hard-codes at main.py:120-122;
 ``ModUNet``: models/mod.py:9-66; ``UNet``: models/model.py, the BASELINE network and the
@@ -104,6 +106,12 @@ def get_parser(argv=None):
     p.add_argument("--lesion_metrics", action="store_true",
                    help="test: also report lesion-level recall, precision and false-positive "
                         "components per image (of the cleaned masks when a --pp_* option is set)")
+    p.add_argument("--tta", default="none", choices=("none", "hflip", "flips", "d4"),
+                   help="test: also predict the flipped (hflip: 2 views, flips: 4) or flipped and "
+                        "rotated (d4: 8) images, un-warp and merge on the GPU; a second block reports "
+                        "the merged masks, and --surface_metrics / --pp_* / --lesion_metrics read them")
+    p.add_argument("--tta_merge", default="prob", choices=("prob", "logit"),
+                   help="--tta: average the views' probabilities (prob) or their logits (logit)")
     return p.parse_args(argv)
 
 
@@ -206,7 +214,14 @@ def main(args):
     if args.mode in ("train", "both"):
         trainer.train()
     if args.mode in ("test", "both"):
-        trainer.test()
+        if args.tta == "none":
+            trainer.test()
+        else:
+            from unet_hip import HipError
+            try:
+                trainer.test()
+            except (HipError, ValueError) as e:  # e.g. a rotated view of a non-square batch
+                raise SystemExit(f"--tta {args.tta} --tta_merge {args.tta_merge}: {e}")
 
 
 if __name__ == "__main__":

@@ -328,3 +328,116 @@ def lesion_metrics_host(pred, targets, connectivity=1, kind=None):
     out = torch.empty((N, 4), dtype=torch.int64)
     _cc_host_call("unet_lesion_stats_host", p, k, t, N, C, H, W, int(connectivity), out)
     return {f: out[:, i] for i, f in enumerate(LESION_FIELDS)}
+
+
+# ---------------------------------------------------------------- test-time augmentation
+TTA_SETS = {"hflip": 0x03, "flips": 0x0F, "d4": 0xFF}
+TTA_MODES = {"logit": 0, "prob": 1}
+
+
+def tta_view_mask(views):
+    """The bit mask (bit k = view k) of a named set ("hflip", "flips", "d4"), an iterable of view
+    numbers or a mask.  View k: h = k & 1, v = k >> 1 & 1, t = k >> 2 & 1 and
+    T_k(x) = x, transposed if t, then flipped vertically if v, then horizontally if h."""
+    if isinstance(views, str):
+        if views not in TTA_SETS:
+            raise ValueError(f"views must be one of {sorted(TTA_SETS)}, a mask or view numbers, got {views!r}")
+        return TTA_SETS[views]
+    if isinstance(views, int):
+        return views
+    m = 0
+    for k in views:
+        if not 0 <= int(k) <= 7:
+            raise ValueError(f"a view number must be in 0..7, got {k}")
+        m |= 1 << int(k)
+    return m
+
+
+def tta_view_numbers(views):
+    """The view numbers of a set, ascending: the order of the stacked views."""
+    m = tta_view_mask(views)
+    return [k for k in range(8) if m >> k & 1]
+
+
+def _tta_mode(mode):
+    if mode not in TTA_MODES:
+        raise ValueError(f"mode must be one of {sorted(TTA_MODES)}, got {mode!r}")
+    return TTA_MODES[mode]
+
+
+def _tta_4d(x, what):
+    if x.dim() != 4:
+        raise ValueError(f"{what} must be (N, C, H, W), got {tuple(x.shape)}")
+    x = x.detach()
+    # a float32 view is passed as it is (a 4-byte aligned base is legal)
+    return x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous()
+
+
+def _tta_split(logits, n, views):
+    m = tta_view_mask(views)
+    K = bin(m & 0xFF).count("1")
+    if K and logits.shape[0] != K * int(n):
+        raise ValueError(f"logits hold {logits.shape[0]} planes, expected {K} views x {n} samples")
+    return m
+
+
+def tta_views(x, views):
+    """The test-time-augmentation views of x (N, C, H, W) on the device and the current stream:
+    (K N, C, H, W), view-major (out[q N + n] = T_{k_q}(x[n]), the views in ascending k).  A pure
+    permutation.  A view with k >= 4 (transpose, quarter turns) needs H == W."""
+    rt = _boundary_runtime(x, "tta_views")
+    return rt.tta_views(_tta_4d(x, "x"), tta_view_mask(views))
+
+
+def tta_views_host(x, views):
+    """``tta_views`` of a CPU tensor through the library's host twin."""
+    _cc_cpu(x, "tta_views_host")
+    x, m = _tta_4d(x, "x"), tta_view_mask(views)
+    N, C, H, W = x.shape
+    out = torch.empty((bin(m & 0xFF).count("1") * N, C, H, W), dtype=torch.float32)
+    _cc_host_call("unet_tta_views_host", x, N, C, H, W, m, out)
+    return out
+
+
+def tta_merge(logits, n, views, mode="prob"):
+    """Un-warp and merge the model's logits of ``tta_views`` ((K n, C, H, W), the same order) in
+    one pass on the device: a dict of (n, C, H, W) tensors ``score`` (float32: the mean over the
+    views of the probabilities for mode "prob", of the logits for "logit", summed in float32 in
+    ascending view order), ``mask`` (uint8: score > 0.5, resp. sigmoid(score) > 0.5 as
+    ``Trainer.test`` forms it) and ``votes`` (uint8: how many views predict foreground)."""
+    rt = _boundary_runtime(logits, "tta_merge")
+    logits = _tta_4d(logits, "logits")
+    m = _tta_split(logits, n, views)
+    score, mask, votes = rt.tta_merge(logits, int(n), m, _tta_mode(mode))
+    return dict(score=score, mask=mask, votes=votes)
+
+
+def tta_merge_host(logits, n, views, mode="prob"):
+    """``tta_merge`` of a CPU tensor through the library's host twin."""
+    _cc_cpu(logits, "tta_merge_host")
+    logits = _tta_4d(logits, "logits")
+    m = _tta_split(logits, n, views)
+    _, C, H, W = logits.shape
+    shape = (int(n), C, H, W)
+    score = torch.empty(shape, dtype=torch.float32)
+    mask = torch.empty(shape, dtype=torch.uint8)
+    votes = torch.empty(shape, dtype=torch.uint8)
+    _cc_host_call("unet_tta_merge_host", logits, int(n), C, H, W, m, _tta_mode(mode), score, mask, votes)
+    return dict(score=score, mask=mask, votes=votes)
+
+
+def tta_predict(model, images, views="d4", mode="prob"):
+    """Test-time augmentation of ``model`` on ``images`` (N, C, H, W) on the device: the model
+    runs once per view at the caller's batch size (its workspace does not grow, and the first
+    view of every named set is the plain forward), then the logits are merged.  Returns the dict
+    of ``tta_merge`` plus ``logits``, the (K N, C', H, W) per-view logits (``logits[:N]`` is the
+    first view's)."""
+    m = tta_view_mask(views)
+    _tta_mode(mode)
+    v = tta_views(images, m)
+    N = images.shape[0]
+    with torch.no_grad():
+        logits = torch.cat([model(v[q * N:(q + 1) * N]).detach().float() for q in range(v.shape[0] // N)])
+    out = tta_merge(logits, N, m, mode)
+    out["logits"] = logits
+    return out

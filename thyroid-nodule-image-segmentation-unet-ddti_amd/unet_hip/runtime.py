@@ -254,6 +254,29 @@ class UNetRuntime:
         _lib.check(rc, self.ctx, "unet_lesion_stats")
         return out
 
+    def tta_views(self, x, views):
+        """(K N, C, H, W): the views of x (N, C, H, W) in ascending k, view-major (unet_tta_views;
+        views is the bit mask)."""
+        N, C, H, W = x.shape
+        out = torch.empty((bin(views).count("1") * N, C, H, W), dtype=torch.float32, device=x.device)
+        rc = self.lib.unet_tta_views(self.ctx, _lib.ptr(x), N, C, H, W, views, _lib.ptr(out),
+                                     _lib.stream_ptr(x.device))
+        _lib.check(rc, self.ctx, "unet_tta_views")
+        return out
+
+    def tta_merge(self, logits, n, views, mode, want_mask=True, want_votes=True):
+        """score float32, mask uint8, votes uint8, each (n, C, H, W) (None where not wanted), of
+        the per-view logits (K n, C, H, W) (unet_tta_merge; mode 0 logit, 1 prob)."""
+        _, C, H, W = logits.shape
+        shape = (n, C, H, W)
+        score = torch.empty(shape, dtype=torch.float32, device=logits.device)
+        mask = torch.empty(shape, dtype=torch.uint8, device=logits.device) if want_mask else None
+        votes = torch.empty(shape, dtype=torch.uint8, device=logits.device) if want_votes else None
+        rc = self.lib.unet_tta_merge(self.ctx, _lib.ptr(logits), n, C, H, W, views, mode, _lib.ptr(score),
+                                     _lib.ptr(mask), _lib.ptr(votes), _lib.stream_ptr(logits.device))
+        _lib.check(rc, self.ctx, "unet_tta_merge")
+        return score, mask, votes
+
     def stream_wait_bucket(self, b, stream):
         rc = self.lib.unet_stream_wait_bucket(self.ctx, b, ctypes.c_void_p(stream.cuda_stream))
         _lib.check(rc, self.ctx, "unet_stream_wait_bucket")

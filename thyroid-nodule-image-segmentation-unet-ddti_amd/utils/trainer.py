@@ -33,6 +33,12 @@ What runs where (MI355X-first):
   connected components, keep-largest, small-island removal, hole filling) and a second block of
   ``PP_*`` metrics is reported for the cleaned masks; ``config.lesion_metrics`` adds lesion-level
   recall, precision and false-positive components per image (``unet_hip.lesion_metrics``).
+* ``test()`` with ``config.tta`` (``"hflip"``, ``"flips"``, ``"d4"``; ``config.tta_merge``
+  ``"prob"`` or ``"logit"``): flip / rotation test-time augmentation on the device
+  (``unet_hip.tta_predict``: one forward per view, one fused un-warp + merge).  The raw block is
+  still that of the plain forward (the first view); a ``TTA_*`` block reports the merged mask and
+  the share of pixels the views disagree on, and the surface, ``PP_*`` and lesion blocks and the
+  contour PNGs then read the merged mask.
 """
 import os
 import random
@@ -326,6 +332,15 @@ class Trainer:
             psums = torch.zeros(5, dtype=torch.float64, device=self.device)
         if lesion:  # n_pred, n_gt, gt_hit, pred_hit over the test set
             lsums = torch.zeros(4, dtype=torch.int64, device=self.device)
+        tta = str(getattr(cfg, "tta", None) or "none")
+        tta_mode = str(getattr(cfg, "tta_merge", None) or "prob")
+        tta_on = tta != "none"
+        if tta_on:  # the counts of the merged masks; pixels with 0 < votes < K
+            n_views = len(unet_hip.functional.tta_view_numbers(tta))
+            unet_hip.functional._tta_mode(tta_mode)
+            tcounts = torch.zeros(6, dtype=torch.int64, device=self.device)
+            tdis = torch.zeros(1, dtype=torch.int64, device=self.device)
+        src = " (TTA mask)" if tta_on else ""
         for batch in tqdm(self.test_loader, desc="Testing Model", leave=True):
             if batch is None:  # empty DataParallel shard: nothing to count on this rank
                 keep.append(None)
@@ -333,9 +348,20 @@ class Trainer:
             images, masks = batch
             images = images.to(self.device).float()
             masks = masks.to(self.device).float()
-            logits = self.model(images)
+            if tta_on:  # the first view is the identity: its logits are the plain forward's
+                merged = unet_hip.tta_predict(self.model, images, tta, tta_mode)
+                logits = merged["logits"][:images.size(0)]
+            else:
+                logits = self.model(images)
             mask = torch.empty(logits.shape, dtype=torch.uint8, device=self.device)
             self.rt.mask_counts(logits, masks, counts, mask)
+            if tta_on:
+                # the merged mask as +-1 logits, so that every kernel downstream reads the mask
+                # the merge formed (in "prob" mode the score is a probability, not a logit)
+                mask = merged["mask"]
+                logits = mask.float() * 2 - 1
+                self.rt.mask_counts(logits, masks, tcounts)
+                tdis += ((merged["votes"] > 0) & (merged["votes"] < n_views)).sum()
             if surface:
                 ssums += self._surface_sums(logits, masks)
             if post:
@@ -362,13 +388,30 @@ class Trainer:
         if self.rank0:
             print(msg)
         self.logger.info(msg)
+        if tta_on:
+            tm = global_metrics_from_counts(self._reduce_counts(tcounts).tolist())
+            if _distributed():
+                dist.all_reduce(tdis)
+            n_dis = int(tdis.item())  # the one transfer
+            n_pix = tm["TP"] + tm["FP"] + tm["FN"] + tm["TN"]
+            dis = n_dis / n_pix if n_pix else float("nan")
+            tmsg = (f"TTA ({tta}, {tta_mode})\n"
+                    f"  TP={tm['TP']}, FP={tm['FP']}, FN={tm['FN']}, TN={tm['TN']}\n"
+                    f"  ACC={tm['ACC']:.4f}, Precision={tm['Precision']:.4f}, "
+                    f"Recall={tm['Recall']:.4f}, F1={tm['F1']:.4f}, IoU={tm['IoU']:.4f}\n"
+                    f"  Disagreement={dis:.4f} ({n_dis} of {n_pix} pixels, {n_views} views)")
+            if self.rank0:
+                print(tmsg)
+            self.logger.info(tmsg)
+            m.update({"TTA_" + k: v for k, v in tm.items()})
+            m["TTA_Disagreement"] = dis
         if surface:
             if _distributed():
                 dist.all_reduce(ssums)
             hd95, hd, assd, k, u = ssums.tolist()  # the one transfer
             k, u = int(k), int(u)
             hd95, hd, assd = ((v / k if k else float("nan")) for v in (hd95, hd, assd))
-            smsg = (f"Surface Metrics — HD95={hd95:.4f}, HD={hd:.4f}, ASSD={assd:.4f} px "
+            smsg = (f"Surface Metrics{src} — HD95={hd95:.4f}, HD={hd:.4f}, ASSD={assd:.4f} px "
                     f"over {k} of {total} images ({u} undefined)")
             if self.rank0:
                 print(smsg)
@@ -377,7 +420,7 @@ class Trainer:
         if post:
             pm = global_metrics_from_counts(self._reduce_counts(pcounts).tolist())
             pmsg = (f"Post-processed (largest={int(pp['keep_largest'])}, min_area={pp['min_area']}, "
-                    f"fill_holes={int(pp['fill_holes'])}, connectivity={pp['connectivity']})\n"
+                    f"fill_holes={int(pp['fill_holes'])}, connectivity={pp['connectivity']}){src}\n"
                     f"  TP={pm['TP']}, FP={pm['FP']}, FN={pm['FN']}, TN={pm['TN']}\n"
                     f"  ACC={pm['ACC']:.4f}, Precision={pm['Precision']:.4f}, "
                     f"Recall={pm['Recall']:.4f}, F1={pm['F1']:.4f}, IoU={pm['IoU']:.4f}")
@@ -402,7 +445,8 @@ class Trainer:
             rec = gt_hit / n_gt if n_gt else nan
             prec = pred_hit / n_pred if n_pred else nan
             fpc = (n_pred - pred_hit) / total if total else nan
-            lmsg = (f"Lesion Metrics ({'post-processed' if post else 'raw'} masks, connectivity "
+            lmsg = (f"Lesion Metrics ({('post-processed' if post else 'raw') + (' TTA' if tta_on else '')} "
+                    f"masks, connectivity "
                     f"{pp['connectivity']}) — Recall={rec:.4f} ({gt_hit}/{n_gt}), Precision={prec:.4f} "
                     f"({pred_hit}/{n_pred}), FP components/image={fpc:.4f}")
             if self.rank0:
