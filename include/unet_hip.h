@@ -146,7 +146,21 @@ int unet_num_bn(const unet_ctx* ctx, int* n_layers, int64_t* n_floats);
 int unet_bn_info(const unet_ctx* ctx, int i, const char** name, int* channels, int64_t* offset);
 
 /* Bytes of device workspace for one forward (+backward when training) at (N, H, W).
- * H and W must be multiples of max(16, 2**depth). */
+ * H and W must be multiples of max(16, 2**depth).  The size depends on the configuration, the
+ * shape, `training` and the schedule options (unet_set_option) in force at the call, and on
+ * nothing else: ask again after changing an option.
+ *
+ * The workspace contract of unet_forward / unet_backward:
+ *   - `workspace` must be 256-byte aligned (hipMalloc and torch's allocator give more).  The
+ *     planner places every region at a multiple of 256 bytes from the base, and the kernels read
+ *     them with 16-byte loads and LDS-DMA; a misaligned base is UNET_ERR_INVALID, and fewer than
+ *     unet_workspace_size bytes UNET_ERR_WORKSPACE, both before any device work.
+ *   - Its contents on entry do not matter: a forward reads nothing from it that it (or, with the
+ *     fused AdamW, unet_adamw_repack) has not written, whatever bytes an earlier tenant left,
+ *     NaN patterns included.  A backward reads only what the training forward on the same
+ *     workspace and the backward itself wrote.
+ *   - Nothing outside [workspace, workspace + unet_workspace_size) is written, apart from the
+ *     outputs named below (logits, the BN buffers of a training forward, grads). */
 int unet_workspace_size(unet_ctx* ctx, int N, int H, int W, int training, size_t* bytes);
 
 /* Forward.  params: flat arena; bn_running: running-stat arena (updated when training);

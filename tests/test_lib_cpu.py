@@ -421,3 +421,117 @@ def test_backward_refuses_without_a_training_forward(rt):
     rc = fresh.lib.unet_backward(fresh.ctx, d, d, d, d, 1 << 30, 2, 64, 64, None)
     assert rc == -1
     assert b"without a training forward" in fresh.lib.unet_last_error(fresh.ctx)
+
+
+# ---------------------------------------------------------------- the workspace contract
+# unet_forward / unet_backward validate the workspace (alignment, size) and the shape before
+# their first HIP call, so the refusals run without a device on placeholder pointers that are
+# never dereferenced.  Each call below is one that must be refused: none reaches a launch.
+def _ws_contexts():
+    import workspace_cases as WC
+    return [WC.CASES[0], WC.CASES[4], WC.CASES[8]]  # model, channel-padded mod, res
+
+
+def _fwd_rc(rt, ws_addr, ws_bytes, N, H, W, training):
+    d = ctypes.c_void_p(1 << 20)
+    rc = rt.lib.unet_forward(rt.ctx, d, d, d, d, d, ctypes.c_void_p(ws_addr), ws_bytes, N, H, W,
+                             int(training), None)
+    return rc, (rt.lib.unet_last_error(rt.ctx) or b"").decode()
+
+
+@pytest.mark.parametrize("i", range(3))
+def test_short_workspace_is_refused(i):
+    """ws_bytes = unet_workspace_size - 1 is UNET_ERR_WORKSPACE, for training and inference, and
+    so is an inference-sized workspace handed to a training forward; the text names both sizes."""
+    import workspace_cases as WC
+    c = _ws_contexts()[i]
+    rt = WC.runtime(c)
+    tr, ev = rt.workspace_bytes(c.N, c.H, c.W, True), rt.workspace_bytes(c.N, c.H, c.W, False)
+    assert ev < tr
+    for training, have, need in ((True, tr - 1, tr), (False, ev - 1, ev), (True, ev, tr), (True, 0, tr)):
+        rc, msg = _fwd_rc(rt, 1 << 30, have, c.N, c.H, c.W, training)
+        assert rc == -4, (rc, msg)
+        assert str(have) in msg and str(need) in msg, msg
+
+
+@pytest.mark.parametrize("i", range(3))
+@pytest.mark.parametrize("delta", [4, 16, 128, 255])
+def test_misaligned_workspace_is_refused(i, delta):
+    """include/unet_hip.h: the workspace base is 256-byte aligned.  base + 4 and base + 16 (aligned
+    enough for every load the kernels issue from a region's start, not for the planner's offsets)
+    are UNET_ERR_INVALID from unet_forward and unet_backward, however large the workspace."""
+    import workspace_cases as WC
+    c = _ws_contexts()[i]
+    rt = WC.runtime(c)
+    rc, msg = _fwd_rc(rt, (1 << 30) + delta, 1 << 40, c.N, c.H, c.W, True)
+    assert rc == -1 and "aligned" in msg, (rc, msg)
+    d = ctypes.c_void_p(1 << 20)
+    rc = rt.lib.unet_backward(rt.ctx, d, d, d, ctypes.c_void_p((1 << 30) + delta), 1 << 40, c.N, c.H,
+                              c.W, None)
+    assert rc == -1 and b"aligned" in rt.lib.unet_last_error(rt.ctx)
+
+
+def test_refused_shapes_never_reach_the_workspace():
+    """Shapes below the shape contract (H, W multiples of max(16, 2**depth)) are UNET_ERR_SHAPE
+    from unet_workspace_size and from unet_forward, whatever workspace comes with them."""
+    import workspace_cases as WC
+    from unet_hip._lib import HipError
+    for c in WC.REFUSED_SHAPES:
+        rt = WC.runtime(c)
+        with pytest.raises(HipError, match="UNET_ERR_SHAPE"):
+            rt.workspace_bytes(c.N, c.H, c.W, True)
+        rc, msg = _fwd_rc(rt, 1 << 30, 1 << 40, c.N, c.H, c.W, True)
+        assert rc == -2, (rc, msg)
+
+
+def test_workspace_size_grows_with_the_shape():
+    """Over the case table: the plan grows with N, H and W (every activation region does, by more
+    than the planner's 256-byte rounding), training needs more than inference, and the size is a
+    function of configuration, shape and options alone (a second context agrees)."""
+    import workspace_cases as WC
+    for c in WC.CASES:
+        rt = WC.runtime(c)
+        q = 1 << max(c.depth, 4)
+        for training in (True, False):
+            nb = rt.workspace_bytes(c.N, c.H, c.W, training)
+            for N, H, W in ((c.N + 1, c.H, c.W), (c.N, c.H + q, c.W), (c.N, c.H, c.W + q)):
+                assert rt.workspace_bytes(N, H, W, training) > nb, (WC.case_id(c), N, H, W, training)
+        assert rt.workspace_bytes(c.N, c.H, c.W, True) > rt.workspace_bytes(c.N, c.H, c.W, False)
+
+
+def test_workspace_size_is_a_function_of_the_configuration():
+    import workspace_cases as WC
+    from _helpers import options
+    from unet_hip import _lib
+    from unet_hip.runtime import UNetRuntime
+    for c in (WC.CASES[1], WC.CASES[4], WC.CASES[6], WC.CASES[10]):
+        rt = WC.runtime(c)
+        math = _lib.MATH_BF16 if c.math == "bf16" else _lib.MATH_F32
+        variant = {"model": _lib.VARIANT_MODEL, "mod": _lib.VARIANT_MOD, "res": _lib.VARIANT_RES}[c.net]
+        base, depth = (0, 0) if c.net == "model" else (c.base, c.depth)
+        other = UNetRuntime("cuda:0", 1, c.out_ch, variant, base, depth, math)
+        for kv in WC.option_settings(c):
+            for k, v in kv.items():
+                other.set_option(k, v)
+            with options(rt, **kv):
+                for training in (True, False):
+                    assert (rt.workspace_bytes(c.N, c.H, c.W, training) ==
+                            other.workspace_bytes(c.N, c.H, c.W, training)), (WC.case_id(c), kv)
+            other.reset_options()
+
+
+def test_option_probe_covers_the_plan_changing_settings():
+    """tests/workspace_cases.py option_settings: the default first, single-option settings only,
+    the f32 cases with the settings the issue names, and the runtime's options left alone."""
+    import workspace_cases as WC
+    for c in WC.CASES:
+        rt = WC.runtime(c)
+        before = {k: rt.get_option(k) for k in rt._default_options}
+        s = WC.option_settings(c)
+        assert {k: rt.get_option(k) for k in before} == before
+        assert s[0] == {} and all(len(kv) == 1 for kv in s[1:])
+        assert len({WC.settings_id(kv) for kv in s}) == len(s)
+        if c.math == "fp32":
+            for kv in ({"x3": 0}, {"dz_in_wgrad": 0}, {"convt16": 0}, {"rg16": 0}, {"head_fuse": 0},
+                       {"pool_fuse": 0}, {"wgrad_row3": 0}):
+                assert kv in s, (WC.case_id(c), kv)

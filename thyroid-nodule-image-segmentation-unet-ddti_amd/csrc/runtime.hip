@@ -667,12 +667,19 @@ struct Plan {
     size_t bytes;
 };
 
+// Every region starts at a multiple of WS_ALIGN bytes from the workspace base, and the
+// kernels read the regions with 16-byte loads and LDS-DMA: the base itself must be aligned
+// (unet_forward / unet_backward refuse one that is not).
+constexpr int WS_ALIGN = 256;
+
+inline bool ws_aligned(const void* ws) { return ((uintptr_t)ws & (WS_ALIGN - 1)) == 0; }
+
 struct Bump {
     char* base;
     size_t off = 0;
     template <class T>
     T* take(int64_t n) {
-        off = (off + 255) & ~(size_t)255;
+        off = (off + WS_ALIGN - 1) & ~(size_t)(WS_ALIGN - 1);
         T* p = base ? (T*)(base + off) : nullptr;
         off += (size_t)n * sizeof(T);
         return p;
@@ -2612,6 +2619,7 @@ int unet_forward(unet_ctx* c, const float* params, float* bn_running, int64_t* b
                  int training, unet_stream_t stream) {
     ABI_TRY
     if (!c || !params || !x || !logits || !ws) return c ? fail(c, UNET_ERR_INVALID, "null pointer") : UNET_ERR_INVALID;
+    if (!ws_aligned(ws)) return fail(c, UNET_ERR_INVALID, "workspace %p is not %d-byte aligned", ws, WS_ALIGN);
     if (!shape_ok(c, N, H, W)) return fail(c, UNET_ERR_SHAPE, "bad shape N=%d H=%d W=%d", N, H, W);
     if (!training && !bn_running)
         return fail(c, UNET_ERR_INVALID, "eval forward needs running statistics");
@@ -2645,6 +2653,7 @@ int unet_backward(unet_ctx* c, const float* params, const float* dlogits, float*
                   size_t ws_bytes, int N, int H, int W, unet_stream_t stream) {
     ABI_TRY
     if (!c || !params || !dlogits || !grads || !ws) return c ? fail(c, UNET_ERR_INVALID, "null pointer") : UNET_ERR_INVALID;
+    if (!ws_aligned(ws)) return fail(c, UNET_ERR_INVALID, "workspace %p is not %d-byte aligned", ws, WS_ALIGN);
     if (!shape_ok(c, N, H, W)) return fail(c, UNET_ERR_SHAPE, "bad shape N=%d H=%d W=%d", N, H, W);
     const unet_ctx::FwdRec* rec = find_fwd(c, ws);
     if (!rec) return fail(c, UNET_ERR_INVALID, "backward without a training forward on this workspace");
