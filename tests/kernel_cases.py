@@ -1,0 +1,164 @@
+"""Which GEMM kernels the bench.py configurations launch, and the small fp64-checked cases
+that stand for them (tests/test_gpu_kernel_coverage.py; helper of the tests, not a test;
+importable without a GPU).
+
+runtime.hip chooses the kernel and tile of every conv / ConvT / skip GEMM from the shape and
+the CU count (x3_tile, x3_wgrad_cfg, rg16_tile, wgrad_cfg, pick_tile, wg16_tile,
+convt_wg16_on), by block-count thresholds the suite's 64^2 / 128^2 inputs never reach.  The
+library reports every launch as ``family/kernel_tile|layer`` (rt.timing_records()).  `key`
+reduces such a label to what a small case has to reproduce to stand for it:
+
+    (family, kernel_tile, row_class)
+
+row_class applies to the kernels that walk whole image rows -- the tap-row halo row GEMMs
+(label ``...r3_BMxBN``: BM pixels per tile) and the tap-row weight gradients (``wx3r3``,
+``wg16r3`` / ``wg16r3m``, ``wgrad3``: the pixels of one K chunk, 32 for the x3 and f32 kernels
+-- the f32 label carries it -- and 64 for the bf16 kernel).  It is how the layer's row width
+W >> level relates to that count, because these kernels take another path for each:
+"lt" several image rows per tile, "eq", "gt" several tiles per image row.  Every other
+kernel gets "-".  Split-K counts, XCD block order and tile grouping are not in the label and
+not in the key (the bit-identity tests hold those).
+
+PRODUCTION: the configurations bench.py can time, at its own batch and image sizes.
+SMALL: the small cases; each forces the kernels under test through schedule options (the
+forcing rules of runtime.hip accept any tile that fits) at the smallest shape at which the
+kernel still meets its edges.
+"""
+import re
+
+GEMM_FAMILIES = tuple(f"{a}_{b}" for a in ("conv", "convT", "skip") for b in ("fwd", "dgrad", "wgrad"))
+
+# bench.py: config 2 = UNet, bs 32 at 256^2; config 4 = ModUNet(128, 5), bs 8 at 512^2, --mfma
+# fp32 / bf16; --config res = ResUNet(--base, --depth), bs 16 at 512^2, f32 only (--mfma is
+# config 4's): the reference grid's bases at depth 4 and bench.py's own default (64, 5)
+PRODUCTION = [
+    dict(id="c2", net="unet", base=64, depth=4, math="fp32", shape=(32, 256, 256)),
+    dict(id="c4_fp32", net="mod", base=128, depth=5, math="fp32", shape=(8, 512, 512)),
+    dict(id="c4_bf16", net="mod", base=128, depth=5, math="bf16", shape=(8, 512, 512)),
+    dict(id="res16", net="res", base=16, depth=4, math="fp32", shape=(16, 512, 512)),
+    dict(id="res24", net="res", base=24, depth=4, math="fp32", shape=(16, 512, 512)),
+    dict(id="res32", net="res", base=32, depth=4, math="fp32", shape=(16, 512, 512)),
+    dict(id="res48", net="res", base=48, depth=4, math="fp32", shape=(16, 512, 512)),
+    dict(id="res64", net="res", base=64, depth=4, math="fp32", shape=(16, 512, 512)),
+    dict(id="res64_d5", net="res", base=64, depth=5, math="fp32", shape=(16, 512, 512)),
+]
+
+MAX_PIXELS = 128 * 512  # per sample
+MAX_N = 3
+
+
+def level_of(family, layer, depth):
+    """Level of the layer a label names: conv i belongs to block i // 2 (two 3x3 convs per
+    block; blocks 0 .. depth - 1 encoders, depth the bottleneck, then the decoders back up),
+    the skip GEMMs carry the block itself, ConvT 100 + k reads level depth - k."""
+    if layer >= 100:
+        return depth - (layer - 100)
+    b = layer if family.startswith("skip") else layer // 2
+    return b if b <= depth else 2 * depth - b
+
+
+_ROWS = (
+    (re.compile(r"^x3r3_(\d+)x\d+$"), None),          # x3 halo row GEMM: BM
+    (re.compile(r"^rg16r3_(\d+)x\d+s\d+$"), None),    # bf16 halo row GEMM: BM
+    (re.compile(r"^wx3r3_\d+x\d+$"), 32),             # x3 tap-row wgrad: 32-pixel chunks
+    (re.compile(r"^wg16r3m?_\d+x\d+s\d+$"), 64),      # bf16 tap-row wgrad: 64-pixel chunks
+    (re.compile(r"^wgrad3_\d+x\d+x(\d+)$"), None),    # f32 tap-row wgrad: the chunk it names
+)
+
+
+def tile_rows(kernel):
+    """Pixels one tile (row GEMM) or K chunk (weight gradient) of a row-walking kernel spans,
+    None for every other kernel."""
+    for rx, fixed in _ROWS:
+        m = rx.match(kernel)
+        if m:
+            return fixed if fixed is not None else int(m.group(1))
+    return None
+
+
+def key(label, depth, W):
+    """Coverage key (family, kernel_tile, row_class) of one launch label of a network of
+    `depth` levels run on images W pixels wide."""
+    family, _, rest = label.partition("/")
+    kernel, _, layer = rest.partition("|")
+    rows = tile_rows(kernel)
+    if rows is None or not layer:
+        return (family, kernel, "-")
+    w = W >> level_of(family, int(layer), depth)
+    return (family, kernel, "lt" if w < rows else "eq" if w == rows else "gt")
+
+
+def _case(id, net, base, depth, math, shape, note, **opts):
+    return dict(id=id, net=net, base=base, depth=depth, math=math, shape=shape, opts=opts, note=note)
+
+
+# Shapes: H, W multiples of max(16, 2^depth).  A 256-row tile is "gt" at W = 512, "eq" at W =
+# 256, "lt" below; a 128-row tile at half those widths, so one (1, 16, 512) or (1, 32, 512)
+# step meets all three on its way down the levels.  (1, 48, 80): tiles ending past M, rows
+# that are no power of two (the one-tap kernels only).  N = 3: a tile spans the border
+# between two samples.  (3, 32, 256) at depth 4 / (3, 32, 128) at depth 3: 2 x 16 / 4 x 16
+# pixels at the deepest level, the W >= 16, row_w == 16 and row_w == 32 branches.
+SMALL = [
+    # ---- models/model.py UNet, f32 (x3): masked-fp64 step of tests/test_gpu_x3.py
+    _case("unet_default", "unet", 64, 4, "fp32", (2, 128, 128),
+          "the default rule at a small grid: 128x128 / 128x64 one-tap tiles, tap-row wgrad "
+          "(shape of test_x3_train_step_matches_f32_mfma)"),
+    _case("unet_halo256", "unet", 64, 4, "fp32", (1, 16, 512),
+          "256x128 halo tile at W = 512 (gt), 256 (eq), 128 .. 32 (lt)", x3_tile=4),
+    _case("unet_halo128", "unet", 64, 4, "fp32", (1, 16, 512),
+          "128x64 halo tile on every 3x3 GEMM: W = 512, 256 (gt), 128 (eq), 64, 32 (lt)",
+          x3_tile=6),
+    _case("unet_halo256_n3", "unet", 64, 4, "fp32", (3, 32, 256),
+          "256x128 halo tile over sample borders, 2 x 16 pixels at the deepest level; 16-pixel "
+          "rows of the tap-row wgrad in pairs", x3_tile=4),
+    _case("unet_halo128_n3", "unet", 64, 4, "fp32", (3, 32, 256),
+          "128x64 halo tile over sample borders, W = 16 rows", x3_tile=6),
+    _case("unet_onetap256", "unet", 64, 4, "fp32", (1, 48, 80),
+          "256x128 / 256x64 one-tap tiles ending past M (shape of "
+          "test_x3_row_tile_choice_bit_identical); one-tap x3 wgrad",
+          x3_tile=0, x3_n64=3, x3_r3=0),
+    _case("unet_wtile64", "unet", 64, 4, "fp32", (2, 32, 64),
+          "64x64 tap-row wgrad on every 3x3 layer, 64x64 one-tap wgrad on the ConvTs", x3_wtile=4),
+    # ---- models/mod.py UNet, f32 (x3): fp32-oracle envelope of test_mod_narrow_full_grads_vs_fp64
+    _case("mod128_default", "mod", 128, 3, "fp32", (2, 64, 64),
+          "config 4's widths at the default rule of a small grid"),
+    _case("mod128_halo256", "mod", 128, 3, "fp32", (1, 16, 512),
+          "256x128 halo tile with the BN -> ReLU epilogues: gt / eq / lt", x3_tile=4),
+    _case("mod128_halo256_n3", "mod", 128, 3, "fp32", (3, 32, 128),
+          "... over sample borders, 4 x 16 pixels at the deepest level", x3_tile=4),
+    _case("mod128_onetap256", "mod", 128, 3, "fp32", (1, 48, 80),
+          "256x128 one-tap tile ending past M", x3_tile=0, x3_r3=0),
+    # ---- models/mod.py UNet, bf16: bf16-operand oracle of test_mod_bf16_matches_bf16_oracle
+    _case("mod128_bf16_default", "mod", 128, 3, "bf16", (2, 64, 64),
+          "128x128 LDS-DMA tile (small grid), tap-row wgrad at W = 64 (eq), 32, 16 (lt)"),
+    _case("mod128_bf16_halo256", "mod", 128, 3, "bf16", (1, 16, 512),
+          "256x256 halo tile: gt / eq / lt; tap-row wgrad gt", rg16_tile=19),
+    _case("mod128_bf16_halo512", "mod", 128, 3, "bf16", (1, 16, 512),
+          "512x128 halo tile: eq at W = 512, lt below", rg16_tile=20),
+    _case("mod128_bf16_halo256_n3", "mod", 128, 3, "bf16", (3, 32, 128),
+          "256x256 halo tile over sample borders, 4 x 16 pixels at the deepest level",
+          rg16_tile=19),
+    _case("mod128_bf16_256x128", "mod", 128, 3, "bf16", (1, 48, 80),
+          "256x128 one-tap tile ending past M; one-tap 256x256 wgrad (W = 80)", rg16_tile=2),
+    _case("mod128_bf16_256x256", "mod", 128, 3, "bf16", (1, 48, 80),
+          "256x256 one-tap tile ending past M (128-output GEMMs: 128x128)", rg16_tile=4),
+    _case("mod128_bf16_512x128", "mod", 128, 3, "bf16", (3, 16, 48),
+          "512x128 one-tap tile ending past M, over sample borders", rg16_tile=6),
+    # ---- models/mod.py ResUNet, f32: envelope of test_res_full_grads_vs_oracle
+    _case("res16_default", "res", 16, 4, "fp32", (1, 32, 128),
+          "padded 16 -> 32: 32-channel f32 MFMA tiles and tap-row wgrads (W = 128, 64: gt), skip "
+          "GEMMs"),
+    _case("res24_default", "res", 24, 4, "fp32", (1, 32, 128), "padded 24 / 48 / 96"),
+    _case("res32_halo128", "res", 32, 4, "fp32", (1, 16, 512),
+          "128x64 halo tile on the 64-channel level (W = 256: gt) next to the 32-channel level",
+          x3_tile=6),
+    _case("res48_default", "res", 48, 4, "fp32", (3, 16, 48), "padded 48 -> 64, odd N"),
+    _case("res64_halo256", "res", 64, 4, "fp32", (1, 16, 512),
+          "256x128 halo tile with the residual epilogues (E_ADD dgrad)", x3_tile=4),
+    _case("res64_default", "res", 64, 3, "fp32", (2, 64, 64),
+          "the default rule at a small grid (shape of test_res_full_grads_vs_oracle)"),
+]
+
+
+def by_id(cases):
+    return {c["id"]: c for c in cases}
