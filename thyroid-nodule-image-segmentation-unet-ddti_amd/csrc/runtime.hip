@@ -1,7 +1,8 @@
 // Native runtime behind include/unet_hip.h: the layer graph of the reference UNets
 // (models/model.py:UNet and models/mod.py:UNet), the workspace plan (NHWC activations,
 // zero-copy concat buffers, packed weights, backward scratch) and the forward / backward /
-// loss / optimizer orchestration on one HIP stream.
+// optimizer orchestration on one HIP stream.  The context itself is in runtime_internal.h; the
+// entry points that need no graph or plan (losses, metrics, augmentations) are in ops_abi.hip.
 //
 // Both reference networks are the same encoder / bottleneck / decoder topology over
 // depth D levels of C_l = base << l channels:
@@ -16,26 +17,13 @@
 // (:71-131) has the same skeleton with residual blocks ReLU(conv(x) + skip(x)): there the
 // block output is materialised by the 1x1 skip GEMM's epilogue (E_RESID) and every
 // consumer reads it plainly.
-#include <math.h>
 #include <stdlib.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <memory>
-#include <new>
-#include <stdexcept>
-#include <string>
-#include <vector>
 
-#include "../../include/unet_hip.h"
-#include "aug.h"
-#include "cc.h"
-#include "edt.h"
-#include "kernels_misc.h"
-#include "tta.h"
-#include "x3_split.h"
+#include "runtime_internal.h"
 
 namespace {
 
@@ -47,137 +35,7 @@ constexpr int WIDE_G = 2048;          // ... of the level-0 bandwidth passes (mo
 // partial buffers hold P/64 + 1 rows: p.stats / p.part per conv of the level, p.hpart WIDE_G)
 inline int wide_g(int64_t P) { return (int)std::min<int64_t>(WIDE_G, std::max<int64_t>(RED_G, P / 64)); }
 constexpr int STAT_G = 256;           // second level of the BN-stat reduction
-constexpr int MAX_DEPTH = 6;
 
-// A parameter tensor.  shape / off / numel describe the torch tensor in the caller's flat
-// arena (what unet_param_info reports); poff / pshape the same tensor in the context's
-// channel-padded arena (== the torch layout unless the network is padded, see
-// unet_ctx::padded).  Padded dims are segmented: dim k holds nseg[k] segments of seg[k]
-// real entries, each padded to pseg[k] (2 segments for a concat input [skip | up]).
-struct ParamT {
-    std::string name;
-    int ndim;
-    int64_t shape[4];
-    int64_t off, numel;
-    int stage;           // backward stage after which its gradient is final
-    int64_t poff, pnumel;
-    int64_t seg[4], pseg[4], nseg[4];
-};
-
-struct ConvL {
-    int cin, cout, level, block, which;
-    int64_t w, b;        // param offsets (b < 0: bias-free conv)
-    int64_t pf, pd;      // packed weight offsets (floats) inside the pack region
-};
-struct BnL {
-    int C;               // channels the kernels see (padded)
-    int rC;              // channels of the torch module (running stats, gamma, beta)
-    int64_t g, b;        // gamma / beta offsets in the (padded) parameter arena
-    int64_t run;         // running_mean offset in the (padded) bn arena (var at run + C)
-    int64_t rrun;        // ... in the caller's bn arena (var at rrun + rC)
-    std::string name;
-};
-struct ConvTL {
-    int cin, cout, in_level;
-    int64_t w, b;
-    int64_t pf, pd;
-};
-
-struct TimeRec {
-    std::string label;
-    hipEvent_t a, b;
-    double flop;
-};
-
-// Kernel-schedule options of one context (unet_set_option).  The defaults are the
-// measured-best schedules; the alternatives exist for A/B runs and tests and are chosen
-// explicitly through the ABI (never from the environment).  None of them changes the
-// numerics except where noted as bit-identical alternatives in DESIGN.md.
-struct Options {
-    int wgrad_row3 = 1;        // f32 3x3 wgrad on the one-row-of-taps kernel: 0 never,
-                               // 1 every eligible layer (default: r02 A/B, conv wgrad
-                               // 27.1 -> 24.4 ms/step), 2 layers with a 64-channel operand
-    int wgrad_row3_tile = -1;  // its tile (>= 20), -1 = by channel counts
-    int wgrad_blocks = 2048;       // split-K target (blocks) of the one-tap f32 weight gradients
-    int rg16_bn_k = 0;             // rg16: E_STORE_BN GEMMs with K below this take the 128x128 tile
-                                   // (8192 until the one-barrier halo kernel, r04: 0 is 1-1.5 %
-                                   // faster on config 4, profiles/r04_c4_barrier_ab.txt)
-    int wgrad16_blocks = 1536;     // split-K target (blocks) of the bf16 weight gradients
-                                   // (config 4 A/B: 1536 +1.4 % over 2048, 1024 -4.7 %)
-    int wgrad_row3_big = 21;       // row3 tile where Cin, Cout % 128 == 0 (-1 = 23)
-    int wgrad_row3_n32 = 1;        // row3 weight gradients for 32-channel operands too (tiles 24..26,
-                                   // one / two waves: the split-K target counts four-wave blocks)
-    int wgrad_row3_blocks = 1536;  // split-K target (blocks) of the row3 weight gradients
-                                   // (r02 sweep 512..2048: 1536 best, 391 vs 386 img/s)
-    int wgrad_tile_w = 0;      // f32 wgrad tile, both channel counts multiples of 128
-    int wgrad_tile_n = 7;      // ... 64-channel layers (64x64, 3 waves/SIMD)
-    int tile_n128 = -1;        // f32 row-GEMM tile, N % 128 == 0 (-1 = pick_tile's default)
-    int tile_n128_dgrad = -1;  // ... dgrad-type
-    int tile_n64 = 19;         // ... N = 64 outputs (forward-type)
-    int tile_n64_dgrad = 25;   // ... N = 64, dgrad-type (pipelined 128x64 at three blocks per
-                               // CU: level-0 dgrads 1.50-1.55 -> 1.40-1.45 ms, r03)
-    int tile_convt64 = 1;      // ConvT forward with 64 output channels (grid N = 256)
-    int tile_n32 = 15;         // f32 row GEMMs with 32 outputs: 15 = 256 x 32 with operands
-                               // straight from global memory (r04, ResUNet(32, 4) 263 -> 282
-                               // img/s, (16, 4) 419 -> 478), 14 = the LDS-staged 256 x 32
-    int tile_convt = -1;       // ConvT forward, >= 128 output channels (-1 = tile_n128's)
-    int tile_convt_dgrad = 26; // ConvT input gradient (-1 = tile_n128_dgrad's; 26 = pipelined
-                               // 128x64 at three blocks per CU: the K = 4 Cout short-K GEMMs
-                               // with their BN-partials epilogue, 1.33 -> 1.15 ms per step)
-    int rg16 = 1;              // bf16 row GEMMs on the LDS-DMA kernel (0: register-staged)
-    int rg16_tile = -1;        // its tile (-1 = per GEMM, rg16_tile())
-    int rg16_n128 = 20;        // rg16 tile of the GEMMs whose N is not a multiple of 256 (the
-                               // 128-output layers; -1 = 128x128, 6 = 512x128, 20 = 512x128 tap-row
-                               // halo for 3x3 convs, 6 elsewhere; r04 config 4: 122.7 -> 124.8
-                               // img/s with 20, 121.9 with 6)
-    int rg16_n128_bn = 0;      // ... also for the short-K E_STORE_BN GEMMs (else 128x128)
-    int rg16_r3 = 1;           // 256x256 3x3-conv GEMMs (W >= 16) on the tap-row halo kernel (tile 19;
-                               // config 4: +0.9..1.2 % over three A/B pairs, r03)
-    int wg16 = 1;              // bf16 3x3 wgrad on the LDS-DMA transposed-read kernel
-    int wg16_tile = 2;         // its tile (2 = 256x256)
-    int convt16 = 1;           // bf16 training: the ConvT forward stores the up half of the
-                               // decoder's concat straight into that conv's bf16 operand image
-                               // (no f32 up half; its prep pass converts the skip half only)
-    int wg16_r3 = 7;           // 3x3 layers with W % 64 == 0 on the tap-row bf16 weight gradient:
-                               // 7 = 16x16x32 MFMAs with the re-read stagger (r06, config 4
-                               // +1.3 % over 4, profiles/r06_c4_wg16_ab.txt; also at W = 32 / 16,
-                               // +1.4 %, r06_c4_deep_wgrad_ab.txt), 4 = 32x32x16, four LDS stages
-                               // (r04: 122.7 -> 125.2 img/s), 0 = off (one-tap kernel)
-    int wg16t = 1;             // bf16 ConvT wgrad on the same kernel
-    int xcd16 = 1;             // XCD-contiguous block order, LDS-DMA kernels
-    int xcd_remap = 1;         // ... f32 GEMMs: 0 none, 1 both (default: r03 PMC, HBM bytes
-                               // per launch rowgemm 128x128 2.21 -> 1.00 GB, row3 wgrad
-                               // 2.02 -> 0.97 GB at equal time), 2 row GEMMs, 3 wgrad
-    int dz_in_wgrad = 256;     // layers with Cin <= this form the BN-backward dz in the weight
-                               // gradient's B' loader, which also stores it for the dgrad (no
-                               // bn_dz pass; f32, both BN orders since r04; 0 = off).  Every A'-tile row of
-                               // blocks re-reads do and y instead of dz, so the fusion pays
-                               // where few A' tiles share a pixel slice (profiles/
-                               // r03_tile_experiments.txt: Cin 64..256 gain, 512..1024 lose)
-    int x3 = 1;                // f32 math: conv / ConvT GEMMs whose channel counts are multiples
-                               // of 64 on the bf16 matrix cores through exact three-way operand
-                               // splits (kernels_gemm_x3.hip; fp64 error below the f32 MFMA
-                               // kernels'); 0 = the f32 MFMA kernels everywhere
-    int x3_tile = -1;          // its row-GEMM tile (-1 = x3_tile())
-    int x3_wtile = -1;         // its weight-gradient tile (-1 = by channel counts)
-    int x3_wblocks = 1536;     // split-K target (blocks) of its 128x128 weight gradients
-    int x3_n64 = 2;            // its row-GEMM tile for 64 outputs (2 = 128x64, 3 = 256x64)
-    int x3_r3 = 1;             // its 256x128 3x3 GEMMs on the tap-row halo kernel (tile 4)
-    int x3_wwaves = 3;         // tap-row x3 weight gradients: split-K so the grid is this many full
-                               // waves of block slots (0 = the x3_wblocks target; r05,
-                               // profiles/r05_wwaves_ab.txt)
-    int x3_wwaves1 = 3;        // the same for the one-tap x3 weight gradients (ConvT, 8x8):
-                               // +0.45 % (profiles/r05_wwaves_ab.txt)
-    int pool_fuse = 1;         // x3 and (r06) bf16 paths: the encoder block's second conv recomputes its `do` from
-                               // the max-pool backward's inputs instead of maxpool_bwd storing it
-    int head_fuse = 1;         // x3 (r05) and bf16 (r06) paths, one output channel: the last conv's dz
-                               // pass recomputes `do` from the head instead of head_bwd storing it
-    int tile_group = 1;        // (r06) row-GEMM tile order of the LDS-DMA kernels (rg16, x3): 1 = grouped
-                               // where the N tiles are many (tile_group_auto), 0 = M-major (r05);
-                               // bit-identical
-    int cc_tile = 1;           // connected components: tile rows (0 = 16, 1 = 32, 2 = 64; 64 columns);
-                               // same labels for every value (profiles/cc_time.txt)
-};
 struct OptionDesc {
     const char* name;
     int Options::*field;
@@ -228,152 +86,6 @@ const OptionDesc OPTION_TABLE[] = {
     {"tile_group", &Options::tile_group},
     {"cc_tile", &Options::cc_tile},
 };
-
-}  // namespace
-
-struct unet_ctx {
-    int device = 0;
-    int cus = 256;  // compute units of the device (split-K sizing by whole waves of block slots)
-    int in_ch = 1, out_ch = 1;
-    int variant = UNET_VARIANT_MODEL;
-    int base = 64, depth = 4;  // base: channels of level 0 as the kernels see them (padded)
-    int rbase = 64;            // base_filters of the reference module (models/mod.py:13)
-    // Narrow networks (base_filters 16 / 24 / 32 / 48 of the reference's model grid,
-    // config/config.yaml) run with every level's channels zero-padded to the next power of
-    // two >= 64, the widths the GEMM tiles and channel-quad kernels are built for.  The
-    // caller's arenas keep the torch layouts; unet_forward / unet_backward expand them
-    // into padded arenas in the workspace (zeros in the padding: zero weights, gamma,
-    // beta, so padded channels stay exactly 0 through BN / ReLU / pooling / ConvT / the
-    // head and add +0 to every real sum) and compact the running stats and gradients back.
-    bool padded = false;
-    bool bn_relu = false;    // BN -> ReLU (mod.py) instead of ReLU -> BN (model.py)
-    bool skip_first = false; // concat [skip, up] (mod.py) instead of [up, skip] (model.py)
-    bool bf16 = false;       // conv GEMMs on bf16 MFMA (f32 accumulate), BASELINE config 4
-    bool res = false;        // residual blocks (mod.py:ResUNet): block outputs materialised
-    std::vector<ParamT> params;
-    int64_t n_param_floats = 0;   // caller's (torch-layout) arena
-    int64_t n_pparam_floats = 0;  // padded arena (== n_param_floats unless padded)
-    std::vector<ConvL> conv;
-    std::vector<BnL> bn;
-    std::vector<ConvTL> convt;
-    std::vector<int64_t> skip_w, skip_pd;  // per block: 1x1 skip weight, its dgrad image
-    std::vector<int64_t> skip_pf;          // bf16 math: its plain bf16 image (skip_pd: bf16 too)
-    int64_t head_w = 0, head_b = 0;
-    int64_t n_bn_floats = 0;      // caller's running-stat arena
-    int64_t n_pbn_floats = 0;     // padded
-    int64_t pack_floats = 0;
-    std::vector<PadDesc> pad_params, pad_bn;  // expand / compact tables (padded only)
-    int64_t pad_max_numel = 0, pad_bn_max = 0;
-    int cmax = 0;
-    std::string err;
-    // buckets (DP overlap): contiguous grad ranges, ready after backward stage bucket_stage
-    std::vector<int64_t> bucket_off, bucket_len;
-    std::vector<int> bucket_stage;
-    std::vector<int> bucket_p0, bucket_p1;     // parameter tensors [p0, p1) of each bucket
-    std::vector<int64_t> bucket_pmax;          // ... their largest padded numel
-    std::vector<hipEvent_t> bucket_ev;
-    // timing
-    bool timing = false;
-    std::string tfilter;  // time only launches whose label contains this (empty = all)
-    std::vector<TimeRec> trec;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-    Options opt;
-    // what unet_backward must know about the training forward it completes, kept per forward
-    // (keyed by its workspace: one context serves every model of its configuration on the
-    // device, and their forwards and backwards interleave).  A host-side table, not a header
-    // in the workspace itself: reading device memory back would cost a synchronisation.
-    //  * opt: the workspace plan and which saved images exist (x3, convt16, the bf16 kernels,
-    //    ...) depend on the options, so the backward refuses to run under different ones (it
-    //    would read saved activations at shifted offsets, or an up half the forward never wrote)
-    //  * used_pp / pp_gen: whether the forward read the context's weight images instead of
-    //    packing into its workspace, and their generation then
-    struct FwdRec {
-        const void* ws;
-        Options opt;
-        bool used_pp;
-        uint64_t pp_gen;
-        uint64_t seq;
-    };
-    static constexpr size_t MAX_FWD_RECS = 64;  // forwards awaiting a backward; the oldest leaves
-    std::vector<FwdRec> fwd_recs;
-    uint64_t fwd_seq = 0;
-    // (r06) weight images written by unet_adamw_repack (AdamW fused into the repack): device
-    // buffers owned by the context, valid (pp_ok) for the parameter arena
-    // [pp_src, pp_src + n_param_floats) under the options they were written with, until that
-    // arena is written otherwise (unet_arena_changed, unet_adamw on an overlapping range,
-    // unet_params_changed), an option changes, or another repack.  pp_gen counts repacks: the
-    // images a forward read stay usable by its backward for as long as the generation stands,
-    // whether or not pp_ok was cleared in between (clearing it rewrites nothing).
-    float* pp = nullptr;
-    uint16_t* pp3 = nullptr;
-    // (r06) per-chunk loss statistics of unet_loss_stats (4 floats per chunk, grown on demand)
-    float* lpart = nullptr;
-    int64_t lpart_n = 0;
-    // BoundaryLoss scratch (unet_edt: any-site flags + g^2; unet_boundary_fwd: chunk sums),
-    // grown on demand without a host synchronisation: an outgrown buffer may still be read by
-    // work in flight, so it is kept until unet_destroy
-    void* bscr = nullptr;
-    size_t bscr_bytes = 0;
-    std::vector<void*> bscr_old;
-    // CLAHE scratch (unet_clahe_u8: tile histograms + tables), grown the same way
-    void* ascr = nullptr;
-    size_t ascr_bytes = 0;
-    // ElasticDeform scratch (unet_elastic_u8: the row pass of both fields), grown the same way
-    void* escr = nullptr;
-    size_t escr_bytes = 0;
-    // surface-metric scratch (unet_surface_stats: border planes, squared distances, gather
-    // partials), grown the same way
-    void* sscr = nullptr;
-    size_t sscr_bytes = 0;
-    // connected-component scratch (unet_components / _postprocess / _lesion_stats: labels, areas
-    // and flags, counts), grown the same way
-    void* cscr = nullptr;
-    size_t cscr_bytes = 0;
-    const float* pp_src = nullptr;
-    bool pp_ok = false;
-    uint64_t pp_gen = 0;
-
-    int nconv() const { return (int)conv.size(); }
-    int chl[MAX_DEPTH + 1] = {};                           // kernel (padded) channels per level
-    int ch(int level) const { return chl[level]; }         // kernel (padded) channels
-    int rch(int level) const { return rbase << level; }   // torch module channels
-    int up_off(int l) const { return skip_first ? ch(l) : 0; }    // CAT_l channel offsets
-    int skip_off(int l) const { return skip_first ? 0 : ch(l); }
-};
-
-namespace {
-
-int fail(unet_ctx* c, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) {
-        try {
-            c->err = buf;
-        } catch (...) {  // out of memory for the message itself: keep the code
-        }
-    }
-    return code;
-}
-
-// Every extern "C" entry runs its body inside ABI_TRY / ABI_CATCH(ctx): no C++ exception
-// (std::bad_alloc from the graph / plan / timing containers, ...) unwinds into the caller.
-#define ABI_TRY try {
-#define ABI_CATCH(ctx)                                                                      \
-    }                                                                                       \
-    catch (const std::bad_alloc&) {                                                         \
-        return fail(const_cast<unet_ctx*>(ctx), UNET_ERR_NOMEM, "out of host memory");       \
-    }                                                                                       \
-    catch (const std::exception& e_) {                                                      \
-        return fail(const_cast<unet_ctx*>(ctx), UNET_ERR_INTERNAL, "internal error: %s",     \
-                    e_.what());                                                             \
-    }                                                                                       \
-    catch (...) {                                                                           \
-        return fail(const_cast<unet_ctx*>(ctx), UNET_ERR_INTERNAL, "internal error");        \
-    }
 
 // Parameter table in the reference's named_parameters() order, layer tables, packing
 // offsets and gradient buckets.
@@ -1138,40 +850,6 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
     }
     p.bytes = b.off + 256;
 }
-
-// ------------------------------------------------------------------------------------
-// launch bookkeeping (optional per-launch HIP-event timing)
-// ------------------------------------------------------------------------------------
-struct Launcher {
-    unet_ctx* c;
-    hipStream_t s;
-    hipEvent_t ev() {
-        if (c->ev_used == c->ev_pool.size()) {
-            hipEvent_t e;
-            (void)hipEventCreate(&e);
-            c->ev_pool.push_back(e);
-        }
-        return c->ev_pool[c->ev_used++];
-    }
-    template <class F>
-    int run(const std::string& label, double flop, F&& f) {
-        hipEvent_t a = nullptr, b = nullptr;
-        const bool timed = c->timing && (c->tfilter.empty() || label.find(c->tfilter) != std::string::npos);
-        if (timed) {
-            a = ev();
-            b = ev();
-            (void)hipEventRecord(a, s);
-        }
-        int r = f();
-        if (r != 0) return fail(c, UNET_ERR_HIP, "%s: launch failed (%d: %s)", label.c_str(), r,
-                                r > 0 ? hipGetErrorString((hipError_t)r) : "bad shape");
-        if (timed) {
-            (void)hipEventRecord(b, s);
-            c->trec.push_back(TimeRec{label, a, b, flop});
-        }
-        return 0;
-    }
-};
 
 // Row-GEMM tile choice for an output width N (tile ids: kernels_gemm.hip ROWGEMM_TILES,
 // 18, 19, 25, 26 = kernels_gemm_pipe.hip).
@@ -2405,47 +2083,6 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
     return 0;
 }
 
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc (libImaging/Resample.c) for the
-// BILINEAR filter (support 1) over the full source extent [0, in_size): same double
-// arithmetic in the same order, then the 22-bit fixed-point conversion.
-int pil_resample_plan(int in_size, int out_size, int32_t* kk, int32_t* bounds) {
-    const double in0 = 0.0, in1 = (double)(float)in_size;
-    double filterscale, scale;
-    filterscale = scale = (double)(in1 - in0) / out_size;
-    if (filterscale < 1.0) filterscale = 1.0;
-    const double support = 1.0 * filterscale;
-    const int ksize = (int)ceil(support) * 2 + 1;
-    if (!kk || !bounds) return ksize;
-    std::vector<double> k(ksize);
-    for (int xx = 0; xx < out_size; ++xx) {
-        const double center = in0 + (xx + 0.5) * scale;
-        double ww = 0.0;
-        const double ss = 1.0 / filterscale;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        int x = 0;
-        for (; x < xmax; ++x) {
-            double a = (x + xmin - center + 0.5) * ss;
-            if (a < 0.0) a = -a;
-            const double w = a < 1.0 ? 1.0 - a : 0.0;
-            k[x] = w;
-            ww += w;
-        }
-        for (x = 0; x < xmax; ++x)
-            if (ww != 0.0) k[x] /= ww;
-        for (; x < ksize; ++x) k[x] = 0;
-        for (x = 0; x < ksize; ++x)
-            kk[(int64_t)xx * ksize + x] = k[x] < 0 ? (int32_t)(-0.5 + k[x] * (1 << (32 - 8 - 2)))
-                                                   : (int32_t)(0.5 + k[x] * (1 << (32 - 8 - 2)));
-        bounds[2 * xx] = xmin;
-        bounds[2 * xx + 1] = xmax;
-    }
-    return ksize;
-}
-
 bool shape_ok(const unet_ctx* c, int N, int H, int W) {
     const int q = 1 << std::max(c->depth, 4);  // every level even; >= 16 (model.py contract)
     return N >= 1 && H >= q && W >= q && H % q == 0 && W % q == 0;
@@ -2544,17 +2181,14 @@ int unet_destroy(unet_ctx* c) {
     if (!c) return UNET_ERR_INVALID;
     for (auto e : c->bucket_ev) (void)hipEventDestroy(e);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->pp || c->pp3 || c->lpart || c->bscr || c->ascr || c->escr || c->sscr || c->cscr) {
+    // (a retired buffer implies a live scratch; nothing allocated: no device call at all)
+    void* const own[] = {c->pp,      c->pp3,       c->loss.p,    c->boundary.p,
+                         c->clahe.p, c->elastic.p, c->surface.p, c->cc.p};
+    if (std::any_of(std::begin(own), std::end(own), [](void* p) { return p != nullptr; })) {
         (void)hipSetDevice(c->device);
-        if (c->pp) (void)hipFree(c->pp);
-        if (c->pp3) (void)hipFree(c->pp3);
-        if (c->lpart) (void)hipFree(c->lpart);
-        if (c->bscr) (void)hipFree(c->bscr);
-        if (c->ascr) (void)hipFree(c->ascr);
-        if (c->escr) (void)hipFree(c->escr);
-        if (c->sscr) (void)hipFree(c->sscr);
-        if (c->cscr) (void)hipFree(c->cscr);
-        for (void* p : c->bscr_old) (void)hipFree(p);
+        for (void* p : own)
+            if (p) (void)hipFree(p);
+        for (void* p : c->retired) (void)hipFree(p);
     }
     delete c;
     return UNET_OK;
@@ -2693,404 +2327,15 @@ int unet_backward(unet_ctx* c, const float* params, const float* dlogits, float*
     ABI_CATCH(c)
 }
 
-int unet_loss_stats(unet_ctx* c, const float* logits, const float* targets, int N, int C, int H,
-                    int W, float* stats, double* sums, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !logits || !targets || !stats || !sums) return UNET_ERR_INVALID;
-    if (N < 1 || C < 1 || H < 1 || W < 1) return fail(c, UNET_ERR_SHAPE, "bad loss shape");
-    const int64_t per = (int64_t)C * H * W, need = 4 * (int64_t)N * loss_groups(per);
-    if (need > c->lpart_n) {
-        if (hipSetDevice(c->device) != hipSuccess) return fail(c, UNET_ERR_HIP, "hipSetDevice");
-        if (c->lpart) {  // a loss pass of an earlier call may still read it
-            (void)hipDeviceSynchronize();
-            (void)hipFree(c->lpart);
-        }
-        c->lpart_n = 0;
-        if (hipMalloc((void**)&c->lpart, sizeof(float) * (size_t)need) != hipSuccess) {
-            c->lpart = nullptr;
-            return fail(c, UNET_ERR_HIP, "hipMalloc: loss partials: %lld floats", (long long)need);
-        }
-        c->lpart_n = need;
-    }
-    int r = k_loss_stats(logits, targets, N, per, stats, sums, c->lpart, (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "loss_stats launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_loss_finalize(unet_ctx* c, const double* sums, float* losses, float fa, float fb,
-                       float fg, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !sums || !losses) return UNET_ERR_INVALID;
-    int r = k_loss_finalize(sums, fa, fb, fg, losses, (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "loss_finalize launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_loss_fwd(unet_ctx* c, const float* logits, const float* targets, int N, int C, int H,
-                  int W, float* stats, double* sums, float* losses, float fa, float fb, float fg,
-                  unet_stream_t stream) {
-    const int r = unet_loss_stats(c, logits, targets, N, C, H, W, stats, sums, stream);
-    return r ? r : unet_loss_finalize(c, sums, losses, fa, fb, fg, stream);
-}
-
-int unet_loss_bwd(unet_ctx* c, const float* logits, const float* targets, int N, int C, int H,
-                  int W, const float* stats, const double* sums, const float* w, float* dlogits,
-                  float fa, float fb, float fg, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !logits || !targets || !stats || !sums || !w || !dlogits) return UNET_ERR_INVALID;
-    if (N < 1 || C < 1 || H < 1 || W < 1) return fail(c, UNET_ERR_SHAPE, "bad loss shape");
-    int r = k_loss_bwd(logits, targets, N, (int64_t)C * H * W, stats, sums, w, fa, fb, fg, dlogits,
-                       (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "loss_bwd launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-// A context-owned scratch of at least `bytes`; never synchronises: the outgrown buffer joins
-// bscr_old (see unet_ctx::bscr)
-static int grow_scratch(unet_ctx* c, void*& buf, size_t& have, size_t bytes, const char* what) {
-    if (bytes <= have) return UNET_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return fail(c, UNET_ERR_HIP, "hipSetDevice");
-    if (buf) c->bscr_old.reserve(c->bscr_old.size() + 1);
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess)
-        return fail(c, UNET_ERR_HIP, "hipMalloc: %s scratch: %zu bytes", what, bytes);
-    if (buf) c->bscr_old.push_back(buf);
-    buf = p;
-    have = bytes;
-    return UNET_OK;
-}
-
-static int boundary_scratch(unet_ctx* c, size_t bytes) {
-    return grow_scratch(c, c->bscr, c->bscr_bytes, bytes, "boundary");
-}
-
-static bool edt_shape_ok(int N, int C, int H, int W) {
-    return N >= 1 && C >= 1 && H >= 1 && W >= 1 && H <= EDT_MAX_SIDE && W <= EDT_MAX_SIDE &&
-           (int64_t)N * std::max(H, W) < (int64_t)1 << 31;
-}
-
-int unet_edt(unet_ctx* c, const float* targets, int N, int C, int H, int W, float* dist,
-             unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !targets || !dist) return UNET_ERR_INVALID;
-    if (!edt_shape_ok(N, C, H, W))
-        return fail(c, UNET_ERR_SHAPE, "edt: N, C, H, W >= 1 and max(H, W) <= %d", EDT_MAX_SIDE);
-    if (int r = boundary_scratch(c, sizeof(int) * (size_t)edt_scratch_ints(N, H, W))) return r;
-    int r = k_edt(targets, N, C, H, W, (int*)c->bscr, dist, (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "edt launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_edt_host(const float* targets, int N, int C, int H, int W, float* dist) {
-    if (!targets || !dist) return UNET_ERR_INVALID;
-    if (!edt_shape_ok(N, C, H, W)) return UNET_ERR_SHAPE;
-    try {
-        std::vector<int> g2((size_t)N * H * W);
-        edt_host(targets, N, C, H, W, g2.data(), dist);
-        return UNET_OK;
-    } catch (const std::bad_alloc&) {
-        return UNET_ERR_NOMEM;
-    } catch (...) {
-        return UNET_ERR_INTERNAL;
-    }
-}
-
-static bool surf_shape_ok(int N, int C, int H, int W) {
-    return N >= 1 && C >= 1 && H >= 1 && W >= 1 && H <= EDT_MAX_SIDE && W <= EDT_MAX_SIDE &&
-           2 * (int64_t)N * std::max(H, W) < (int64_t)1 << 31 &&
-           (int64_t)N * H * W < (int64_t)1 << 36;
-}
-
-int unet_surface_stats(unet_ctx* c, const float* logits, const float* targets, int N, int C, int H,
-                       int W, int64_t* out_i64, double* out_f64, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !logits || !targets || !out_i64 || !out_f64) return UNET_ERR_INVALID;
-    if (!surf_shape_ok(N, C, H, W))
-        return fail(c, UNET_ERR_SHAPE, "surface_stats: N, C, H, W >= 1 and max(H, W) <= %d",
-                    EDT_MAX_SIDE);
-    if (int r = grow_scratch(c, c->sscr, c->sscr_bytes, surf_scratch_bytes(N, H, W), "surface"))
-        return r;
-    int r = k_surface_stats(logits, targets, N, C, H, W, c->sscr, out_i64, out_f64,
-                            (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "surface_stats launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_surface_stats_host(const float* logits, const float* targets, int N, int C, int H, int W,
-                            int64_t* out_i64, double* out_f64) {
-    if (!logits || !targets || !out_i64 || !out_f64) return UNET_ERR_INVALID;
-    if (!surf_shape_ok(N, C, H, W)) return UNET_ERR_SHAPE;
-    try {
-        std::vector<uint8_t> border(2 * (size_t)H * W);
-        std::vector<int> d2(2 * (size_t)H * W);
-        surface_stats_host(logits, targets, N, C, H, W, border.data(), d2.data(), out_i64, out_f64);
-        return UNET_OK;
-    } catch (const std::bad_alloc&) {
-        return UNET_ERR_NOMEM;
-    } catch (...) {
-        return UNET_ERR_INTERNAL;
-    }
-}
-
-// ---- connected components, post-processing, lesion counts (kernels_cc.hip, cc.h) ----
-static const char* cc_args_error(int kind, int N, int C, int H, int W, int conn) {
-    if (conn != 1 && conn != 2) return "connectivity must be 1 or 2";
-    if (kind < 0 || kind > 2) return "kind must be 0 (uint8 mask), 1 (logits) or 2 (targets)";
-    if (N < 1 || C < 1 || H < 1 || W < 1) return "N, C, H, W >= 1";
-    if ((int64_t)H * W >= (int64_t)1 << 31) return "H * W must be below 2^31";
-    return nullptr;
-}
-
-// tile, seam and flatten of `planes` planes read from src (see k_cc_tile) into sc.L at plane q0
-static int cc_label(unet_ctx* c, Launcher& ln, const char* what, const void* src, int kind,
-                    int64_t sample_stride, int q0, int planes, int H, int W, int conn,
-                    const CcScratch& sc, bool areas, bool rows, bool counts) {
-    const int64_t hw = (int64_t)H * W;
-    const int tile = c->opt.cc_tile;
-    int* L = sc.L + q0 * hw;
-    int* area = sc.area + q0 * hw;
-    hipStream_t s = ln.s;
-    const std::string w = what;
-    if (int r = ln.run("cc/tile|" + w, 0, [&] { return k_cc_tile(src, kind, sample_stride, planes, H, W, conn, tile, L, area, s); }))
-        return r;
-    if (int r = ln.run("cc/seam|" + w, 0, [&] { return k_cc_seam(L, planes, H, W, conn, tile, s); })) return r;
-    return ln.run("cc/flatten|" + w, 0, [&] {
-        return k_cc_flatten(L, areas ? area : nullptr, rows ? sc.rowcnt + (int64_t)q0 * H : nullptr,
-                            counts ? sc.cnt + q0 : nullptr, planes, H, W, s);
-    });
-}
-
-static int cc_prepare(unet_ctx* c, const char* what, int N, int planes, int H, int W, hipStream_t s,
-                      CcScratch& sc) {
-    if (!cc_grid_ok(planes, H, W)) return fail(c, UNET_ERR_SHAPE, "%s: batch too large for one launch", what);
-    const size_t need = cc_scratch(nullptr, N, planes, H, W).bytes;
-    if (int r = grow_scratch(c, c->cscr, c->cscr_bytes, need, "components")) return r;
-    sc = cc_scratch(c->cscr, N, planes, H, W);
-    if (hipMemsetAsync(c->cscr, 0, sc.zero_bytes, s) != hipSuccess) return fail(c, UNET_ERR_HIP, "%s: memset", what);
-    return UNET_OK;
-}
-
-int unet_components(unet_ctx* c, const void* src, int kind, int N, int C, int H, int W,
-                    int connectivity, int32_t* labels, int32_t* count, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !src || !labels || !count) return UNET_ERR_INVALID;
-    if (const char* e = cc_args_error(kind, N, C, H, W, connectivity))
-        return fail(c, UNET_ERR_INVALID, "components: %s", e);
-    hipStream_t s = (hipStream_t)stream;
-    CcScratch sc;
-    if (int r = cc_prepare(c, "components", N, N, H, W, s, sc)) return r;
-    Launcher ln{c, s};
-    const int64_t hw = (int64_t)H * W;
-    if (int r = cc_label(c, ln, "components", src, kind, C * hw, 0, N, H, W, connectivity, sc, false, true, false))
-        return r;
-    return ln.run("cc/rank|components", 0,
-                  [&] { return k_cc_rank(sc.L, sc.area, sc.rowcnt, count, N, H, W, labels, s); });
-    ABI_CATCH(c)
-}
-
-int unet_postprocess(unet_ctx* c, const void* src, int kind, int N, int C, int H, int W,
-                     int connectivity, int keep_largest, int64_t min_area, int fill_holes,
-                     uint8_t* out, int64_t* info, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !src || !out || !info) return UNET_ERR_INVALID;
-    if (const char* e = cc_args_error(kind, N, C, H, W, connectivity))
-        return fail(c, UNET_ERR_INVALID, "postprocess: %s", e);
-    if ((const void*)out == src) return fail(c, UNET_ERR_INVALID, "postprocess: out must differ from src");
-    hipStream_t s = (hipStream_t)stream;
-    CcScratch sc;
-    if (int r = cc_prepare(c, "postprocess", N, N, H, W, s, sc)) return r;
-    if (hipMemsetAsync(info, 0, 4 * sizeof(int64_t) * (size_t)N, s) != hipSuccess)
-        return fail(c, UNET_ERR_HIP, "postprocess: memset");
-    Launcher ln{c, s};
-    const int64_t hw = (int64_t)H * W;
-    if (int r = cc_label(c, ln, "postprocess", src, kind, C * hw, 0, N, H, W, connectivity, sc, true, false, true))
-        return r;
-    if (int r = ln.run("cc/select|postprocess", 0,
-                       [&] { return k_cc_select(sc.L, sc.area, min_area, sc.kept, sc.best, N, H, W, s); }))
-        return r;
-    if (int r = ln.run("cc/write|postprocess", 0, [&] {
-            return k_cc_write(sc.L, sc.area, min_area, keep_largest, sc.cnt, sc.kept, sc.best, out, info, N, H, W, s);
-        }))
-        return r;
-    if (!fill_holes) return UNET_OK;
-    // the complement of `out` at connectivity 1; the tile pass leaves the flags (sc.area) zero
-    if (int r = cc_label(c, ln, "fill", out, CC_KIND_U8_ZERO, hw, 0, N, H, W, 1, sc, false, false, false))
-        return r;
-    return ln.run("cc/fill|fill", 0, [&] { return k_cc_fill(sc.L, sc.area, out, info, N, H, W, s); });
-    ABI_CATCH(c)
-}
-
-int unet_lesion_stats(unet_ctx* c, const void* pred, int kind, const float* targets, int N, int C,
-                      int H, int W, int connectivity, int64_t* out, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !pred || !targets || !out) return UNET_ERR_INVALID;
-    if (const char* e = cc_args_error(kind, N, C, H, W, connectivity))
-        return fail(c, UNET_ERR_INVALID, "lesion_stats: %s", e);
-    if (N > (1 << 29)) return fail(c, UNET_ERR_SHAPE, "lesion_stats: batch too large for one launch");
-    hipStream_t s = (hipStream_t)stream;
-    CcScratch sc;
-    if (int r = cc_prepare(c, "lesion_stats", N, 2 * N, H, W, s, sc)) return r;
-    if (hipMemsetAsync(out, 0, 4 * sizeof(int64_t) * (size_t)N, s) != hipSuccess)
-        return fail(c, UNET_ERR_HIP, "lesion_stats: memset");
-    Launcher ln{c, s};
-    const int64_t hw = (int64_t)H * W;
-    if (int r = cc_label(c, ln, "pred", pred, kind, C * hw, 0, N, H, W, connectivity, sc, false, false, false))
-        return r;
-    if (int r = cc_label(c, ln, "targets", targets, CC_KIND_TARGETS, C * hw, N, N, H, W, connectivity, sc,
-                         false, false, false))
-        return r;
-    return ln.run("cc/hits|lesion", 0, [&] { return k_cc_hits(sc.L, sc.area, out, N, H, W, s); });
-    ABI_CATCH(c)
-}
-
-#define CC_HOST_BODY(call)                         \
-    try {                                          \
-        call;                                      \
-        return UNET_OK;                            \
-    } catch (const std::bad_alloc&) {              \
-        return UNET_ERR_NOMEM;                     \
-    } catch (...) {                                \
-        return UNET_ERR_INTERNAL;                  \
-    }
-
-int unet_components_host(const void* src, int kind, int N, int C, int H, int W, int connectivity,
-                         int32_t* labels, int32_t* count) {
-    if (!src || !labels || !count || cc_args_error(kind, N, C, H, W, connectivity)) return UNET_ERR_INVALID;
-    CC_HOST_BODY(components_host(src, kind, N, C, H, W, connectivity, labels, count))
-}
-
-int unet_postprocess_host(const void* src, int kind, int N, int C, int H, int W, int connectivity,
-                          int keep_largest, int64_t min_area, int fill_holes, uint8_t* out,
-                          int64_t* info) {
-    if (!src || !out || !info || (const void*)out == src || cc_args_error(kind, N, C, H, W, connectivity))
-        return UNET_ERR_INVALID;
-    CC_HOST_BODY(postprocess_host(src, kind, N, C, H, W, connectivity, keep_largest, min_area, fill_holes, out, info))
-}
-
-int unet_lesion_stats_host(const void* pred, int kind, const float* targets, int N, int C, int H, int W,
-                           int connectivity, int64_t* out) {
-    if (!pred || !targets || !out || cc_args_error(kind, N, C, H, W, connectivity)) return UNET_ERR_INVALID;
-    CC_HOST_BODY(lesion_stats_host(pred, kind, targets, N, C, H, W, connectivity, out))
-}
-
-// ---- test-time augmentation (kernels_tta.hip, tta.h) ----
-// UNET_OK, or the error code with *msg set
-static int tta_args_error(int N, int C, int H, int W, uint32_t views, const char** msg) {
-    *msg = nullptr;
-    if (views == 0 || (views & ~TTA_ALL_VIEWS)) *msg = "views must be a non-empty mask of the bits 0..7";
-    else if (N < 1 || C < 1 || H < 1 || W < 1) *msg = "N, C, H, W >= 1";
-    else if ((int64_t)H * W >= (int64_t)1 << 31) *msg = "H * W must be below 2^31";
-    if (*msg) return UNET_ERR_INVALID;
-    if ((views & 0xF0u) && H != W) *msg = "a transposed view (k >= 4) needs H == W";
-    else if ((int64_t)tta_view_list(views).K * N * C >= (int64_t)1 << 31) *msg = "K * N * C must be below 2^31";
-    return *msg ? UNET_ERR_SHAPE : UNET_OK;
-}
-
-static bool tta_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
-}
-// does an output of the merge overlap its input?
-static bool tta_merge_aliases(const float* logits, int N, int C, int H, int W, uint32_t views, const float* score,
-                              const uint8_t* mask, const uint8_t* votes) {
-    const size_t n = (size_t)N * C * H * W, in = sizeof(float) * n * tta_view_list(views).K;
-    return tta_overlap(logits, in, score, sizeof(float) * n) || tta_overlap(logits, in, mask, n) ||
-           tta_overlap(logits, in, votes, n);
-}
-
-int unet_tta_views(unet_ctx* c, const float* x, int N, int C, int H, int W, uint32_t views, float* out,
-                   unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !x || !out) return UNET_ERR_INVALID;
-    const char* e;
-    if (int r = tta_args_error(N, C, H, W, views, &e)) return fail(c, r, "tta_views: %s", e);
-    Launcher ln{c, (hipStream_t)stream};
-    return ln.run("tta/views", 0, [&] { return k_tta_views(x, N, C, H, W, views, out, ln.s); });
-    ABI_CATCH(c)
-}
-
-int unet_tta_merge(unet_ctx* c, const float* logits, int N, int C, int H, int W, uint32_t views, int mode,
-                   float* score, uint8_t* mask, uint8_t* votes, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !logits || !score) return UNET_ERR_INVALID;
-    const char* e;
-    if (int r = tta_args_error(N, C, H, W, views, &e)) return fail(c, r, "tta_merge: %s", e);
-    if (mode != TTA_MODE_LOGIT && mode != TTA_MODE_PROB)
-        return fail(c, UNET_ERR_INVALID, "tta_merge: mode must be 0 (logit) or 1 (prob)");
-    if (tta_merge_aliases(logits, N, C, H, W, views, score, mask, votes))
-        return fail(c, UNET_ERR_INVALID, "tta_merge: an output overlaps logits");
-    Launcher ln{c, (hipStream_t)stream};
-    return ln.run("tta/merge", 0,
-                  [&] { return k_tta_merge(logits, N, C, H, W, views, mode, score, mask, votes, ln.s); });
-    ABI_CATCH(c)
-}
-
-int unet_tta_views_host(const float* x, int N, int C, int H, int W, uint32_t views, float* out) {
-    if (!x || !out) return UNET_ERR_INVALID;
-    const char* e;
-    if (int r = tta_args_error(N, C, H, W, views, &e)) return r;
-    CC_HOST_BODY(tta_views_host(x, N, C, H, W, views, out))
-}
-
-int unet_tta_merge_host(const float* logits, int N, int C, int H, int W, uint32_t views, int mode, float* score,
-                        uint8_t* mask, uint8_t* votes) {
-    if (!logits || !score) return UNET_ERR_INVALID;
-    const char* e;
-    if (int r = tta_args_error(N, C, H, W, views, &e)) return r;
-    if ((mode != TTA_MODE_LOGIT && mode != TTA_MODE_PROB) ||
-        tta_merge_aliases(logits, N, C, H, W, views, score, mask, votes))
-        return UNET_ERR_INVALID;
-    CC_HOST_BODY(tta_merge_host(logits, N, C, H, W, views, mode, score, mask, votes))
-}
-
-int unet_boundary_fwd(unet_ctx* c, const float* logits, const float* targets, const float* dist,
-                      int N, int C, int H, int W, double* sum, float* loss, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !logits || !targets || !dist || !sum || !loss) return UNET_ERR_INVALID;
-    if (N < 1 || C < 1 || H < 1 || W < 1) return fail(c, UNET_ERR_SHAPE, "bad loss shape");
-    const int64_t hw = (int64_t)H * W;
-    if (int r = boundary_scratch(c, sizeof(float) * (size_t)N * loss_groups(hw))) return r;
-    int r = k_boundary_fwd(logits, targets, dist, N, C, hw, (float*)c->bscr, sum, loss,
-                           (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "boundary_fwd launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_boundary_bwd(unet_ctx* c, const float* logits, const float* targets, const float* dist,
-                      int N, int C, int H, int W, const float* w, float* dlogits,
-                      unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !logits || !targets || !dist || !w || !dlogits) return UNET_ERR_INVALID;
-    if (N < 1 || C < 1 || H < 1 || W < 1) return fail(c, UNET_ERR_SHAPE, "bad loss shape");
-    int r = k_boundary_bwd(logits, targets, dist, N, C, (int64_t)H * W, w, dlogits,
-                           (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "boundary_bwd launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
 int unet_adamw(unet_ctx* c, float* params, const float* grads, float* m, float* v, int64_t n,
                int step, double lr, double b1, double b2, double eps, double wd, double gscale,
                unet_stream_t stream) {
     ABI_TRY
     if (!c || !params || !grads || !m || !v || n < 0 || step < 1) return UNET_ERR_INVALID;
-    // torch optim/adam.py _single_tensor_adam: every scalar is a Python float (double)
-    // that ATen rounds to float once when it meets the fp32 tensor
-    AdamwScalars a;
-    a.decay = (float)(1.0 - lr * wd);                 // param.mul_(1 - lr * weight_decay)
-    a.w1 = (float)(1.0 - b1);                         // exp_avg.lerp_(grad, 1 - beta1)
-    a.lerp_small = fabs(1.0 - b1) < 0.5 ? 1 : 0;
-    a.b2 = (float)b2;                                 // exp_avg_sq.mul_(beta2)
-    a.w2 = (float)(1.0 - b2);                         // .addcmul_(grad, grad, value=1 - beta2)
-    const double bc1 = 1.0 - pow(b1, (double)step);   // beta1 ** step (Python float pow)
-    const double bc2 = 1.0 - pow(b2, (double)step);
-    a.neg_step = (float)(-(lr / bc1));                // addcdiv_(..., value=-step_size)
-    a.bc2_sqrt = (float)pow(bc2, 0.5);                // bias_correction2 ** 0.5
-    a.eps = (float)eps;                               // .add_(eps)
-    a.gscale = (float)gscale;
     // the plain update packs nothing: the images of an arena it writes into are stale
     if (c->pp_ok && ranges_overlap(params, n, c->pp_src, c->n_param_floats)) c->pp_ok = false;
-    int r = k_adamw(params, grads, m, v, n, a, (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "adamw launch %d", r) : UNET_OK;
+    const AdamwScalars a = adamw_scalars(step, lr, b1, b2, eps, wd, gscale);
+    return launched(c, "adamw", k_adamw(params, grads, m, v, n, a, (hipStream_t)stream));
     ABI_CATCH(c)
 }
 
@@ -3141,24 +2386,13 @@ int unet_adamw_repack(unet_ctx* c, float* params, const float* grads, float* m, 
     }
     if (!gap(at, n)) return fail(c, UNET_ERR_INTERNAL, "adamw range table full");
     rest.cum[rest.n] = cum;
-    AdamwScalars a;  // (as unet_adamw)
-    a.decay = (float)(1.0 - lr * wd);
-    a.w1 = (float)(1.0 - b1);
-    a.lerp_small = fabs(1.0 - b1) < 0.5 ? 1 : 0;
-    a.b2 = (float)b2;
-    a.w2 = (float)(1.0 - b2);
-    const double bc1 = 1.0 - pow(b1, (double)step);
-    const double bc2 = 1.0 - pow(b2, (double)step);
-    a.neg_step = (float)(-(lr / bc1));
-    a.bc2_sqrt = (float)pow(bc2, 0.5);
-    a.eps = (float)eps;
-    a.gscale = (float)gscale;
+    const AdamwScalars a = adamw_scalars(step, lr, b1, b2, eps, wd, gscale);
     const hipStream_t s = (hipStream_t)stream;
     c->pp_ok = false;
     ++c->pp_gen;
     int r = k_pack_adamw(jobs, rest, params, grads, m, v, a, c->pp, c->bf16 ? 1 : 0, s);
     if (!r && x3) r = k_to_x3(c->pp, 32, 0, 32, nullptr, nullptr, 0, c->pack_floats / 32, c->pp3, 32, 0, s);
-    if (r) return fail(c, UNET_ERR_HIP, "adamw repack launch %d", r);
+    if (int e = launched(c, "adamw repack", r)) return e;
     c->pp_src = params;
     c->pp_ok = true;
     return UNET_OK;
@@ -3175,24 +2409,6 @@ int unet_arena_changed(unet_ctx* c, const float* params, int64_t n) {
     if (!c || !params || n < 0) return UNET_ERR_INVALID;
     if (c->pp_ok && ranges_overlap(params, n, c->pp_src, c->n_param_floats)) c->pp_ok = false;
     return UNET_OK;
-}
-
-int unet_x3_split_host(const float* v, int64_t n, uint16_t* out) {
-    if (!v || !out || n < 0 || n % 32) return UNET_ERR_INVALID;
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t r = i / 32, j = i % 32;
-        x3_split(v[i], X3CvtHost{}, out[96 * r + j], out[96 * r + 32 + j], out[96 * r + 64 + j]);
-    }
-    return UNET_OK;
-}
-
-int unet_x3_split_device(unet_ctx* c, const float* v, int64_t n, uint16_t* out, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !v || !out || n < 32 || n % 32) return c ? fail(c, UNET_ERR_INVALID, "x3 split: n") : UNET_ERR_INVALID;
-    if (hipSetDevice(c->device) != hipSuccess) return fail(c, UNET_ERR_HIP, "hipSetDevice");
-    const int r = k_to_x3(v, 32, 0, 32, nullptr, nullptr, 0, n / 32, out, 32, 0, (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "to_x3 launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
 }
 
 int unet_set_option(unet_ctx* c, const char* name, int64_t value) {
@@ -3219,15 +2435,6 @@ int unet_get_option(const unet_ctx* c, const char* name, int64_t* value) {
             return UNET_OK;
         }
     return UNET_ERR_INVALID;
-    ABI_CATCH(c)
-}
-
-int unet_mask_counts(unet_ctx* c, const float* logits, const float* targets, int64_t n,
-                     uint8_t* mask, int64_t* counts, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !logits || !targets || !counts || n < 0) return UNET_ERR_INVALID;
-    int r = k_mask_counts(logits, targets, n, mask, counts, (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "mask_counts launch %d", r) : UNET_OK;
     ABI_CATCH(c)
 }
 
@@ -3319,139 +2526,6 @@ int unet_timing_read(unet_ctx* c, int i, const char** family, int64_t* launches,
     if (flop) *flop = t.flop;
     return UNET_OK;
     ABI_CATCH(c)
-}
-
-int unet_resize_plan(int in_size, int out_size, int32_t* coeffs, int32_t* bounds, int* ksize) {
-    ABI_TRY
-    if (in_size < 1 || out_size < 1 || !ksize) return UNET_ERR_INVALID;
-    *ksize = pil_resample_plan(in_size, out_size, coeffs, bounds);
-    return UNET_OK;
-    ABI_CATCH((unet_ctx*)nullptr)
-}
-
-int unet_resize_u8(unet_ctx* c, const uint8_t* src, int h, int w, float* dst, int oh, int ow,
-                   const int32_t* kh, const int32_t* bh, int ksh, const int32_t* kv,
-                   const int32_t* bv, int ksv, float divisor, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !src || !dst || h < 1 || w < 1 || oh < 1 || ow < 1 || !(divisor > 0.f))
-        return UNET_ERR_INVALID;
-    const int need_h = ow != w, need_v = oh != h;
-    if ((need_h && (!kh || !bh || ksh < 1)) || (need_v && (!kv || !bv || ksv < 1)))
-        return fail(c, UNET_ERR_INVALID, "resize: missing coefficient tables");
-    int r = k_resize_u8(src, h, w, dst, oh, ow, kh, bh, ksh, kv, bv, ksv, need_h, need_v, divisor,
-                        (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "resize launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_augment_u8(unet_ctx* c, const uint8_t* src, int h, int w, uint8_t* dst,
-                    const unet_aug_params* params, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !src || !dst || !params || src == dst) return UNET_ERR_INVALID;
-    if (int r = aug_params_check(params, h, w))
-        return fail(c, r, "augment: plane %d x %d, mode %d, %d TGC bands", h, w, params->mode,
-                    params->num_bins);
-    int r = k_augment_u8(src, h, w, dst, *params, (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "augment launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_augment_u8_host(const uint8_t* src, int h, int w, uint8_t* dst,
-                         const unet_aug_params* params) {
-    if (!src || !dst || !params || src == dst) return UNET_ERR_INVALID;
-    if (int r = aug_params_check(params, h, w)) return r;
-    augment_u8_host(src, h, w, dst, *params);
-    return UNET_OK;
-}
-
-int unet_augment_noise_u8(unet_ctx* c, const uint8_t* src, int h, int w, uint8_t* dst,
-                          const unet_aug_params* params, const double* noise,
-                          unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !src || !dst || !params || src == dst) return UNET_ERR_INVALID;
-    if (int r = aug_params_check(params, h, w))
-        return fail(c, r, "augment: plane %d x %d, mode %d, %d TGC bands", h, w, params->mode,
-                    params->num_bins);
-    int r = k_augment_u8(src, h, w, dst, *params, (hipStream_t)stream, noise);
-    return r ? fail(c, UNET_ERR_HIP, "augment launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_augment_noise_u8_host(const uint8_t* src, int h, int w, uint8_t* dst,
-                               const unet_aug_params* params, const double* noise) {
-    if (!src || !dst || !params || src == dst) return UNET_ERR_INVALID;
-    if (int r = aug_params_check(params, h, w)) return r;
-    augment_u8_host(src, h, w, dst, *params, noise);
-    return UNET_OK;
-}
-
-// both entry points: which planes are asked for, and whether they may be written
-static bool elastic_args_ok(const uint8_t* img, const uint8_t* mask, const uint8_t* img_dst,
-                            const uint8_t* mask_dst, const double* rx, const double* ry,
-                            const unet_elastic_params* p) {
-    return p && rx && ry && (img || mask) && (!img || (img_dst && img_dst != img)) &&
-           (!mask || (mask_dst && mask_dst != mask));
-}
-
-int unet_elastic_u8(unet_ctx* c, const uint8_t* img, const uint8_t* mask, int h, int w,
-                    uint8_t* img_dst, uint8_t* mask_dst, const double* rx, const double* ry,
-                    const unet_elastic_params* params, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !elastic_args_ok(img, mask, img_dst, mask_dst, rx, ry, params)) return UNET_ERR_INVALID;
-    if (int r = elastic_check(params, h, w))
-        return fail(c, r, "elastic: plane %d x %d, ksize %d", h, w, params->ksize);
-    if (int r = grow_scratch(c, c->escr, c->escr_bytes, elastic_scratch_bytes(h, w), "elastic"))
-        return r;
-    int r = k_elastic_u8(img, mask, h, w, img_dst, mask_dst, rx, ry, *params, (double*)c->escr,
-                         (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "elastic launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_elastic_u8_host(const uint8_t* img, const uint8_t* mask, int h, int w, uint8_t* img_dst,
-                         uint8_t* mask_dst, const double* rx, const double* ry,
-                         const unet_elastic_params* params) {
-    if (!elastic_args_ok(img, mask, img_dst, mask_dst, rx, ry, params)) return UNET_ERR_INVALID;
-    if (int r = elastic_check(params, h, w)) return r;
-    try {
-        std::vector<double> tmp(2 * (size_t)h * w);
-        elastic_u8_host(img, mask, h, w, img_dst, mask_dst, rx, ry, *params, tmp.data());
-        return UNET_OK;
-    } catch (const std::bad_alloc&) {
-        return UNET_ERR_NOMEM;
-    } catch (...) {
-        return UNET_ERR_INTERNAL;
-    }
-}
-
-int unet_clahe_u8(unet_ctx* c, const uint8_t* src, int h, int w, uint8_t* dst, double clip, int gx,
-                  int gy, unet_stream_t stream) {
-    ABI_TRY
-    if (!c || !src || !dst) return UNET_ERR_INVALID;
-    ClaheGeom G;
-    if (int r = clahe_geom(h, w, clip, gx, gy, G))
-        return fail(c, r, "clahe: plane %d x %d, grid %d x %d", h, w, gx, gy);
-    if (int r = grow_scratch(c, c->ascr, c->ascr_bytes, clahe_scratch_bytes(G), "clahe")) return r;
-    int r = k_clahe_u8(src, dst, G, c->ascr, (hipStream_t)stream);
-    return r ? fail(c, UNET_ERR_HIP, "clahe launch %d", r) : UNET_OK;
-    ABI_CATCH(c)
-}
-
-int unet_clahe_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, double clip, int gx,
-                       int gy) {
-    if (!src || !dst) return UNET_ERR_INVALID;
-    ClaheGeom G;
-    if (int r = clahe_geom(h, w, clip, gx, gy, G)) return r;
-    try {
-        std::vector<int> hist((size_t)gx * gy * 256);
-        std::vector<uint8_t> lut((size_t)gx * gy * 256);
-        clahe_u8_host(src, dst, G, hist.data(), lut.data());
-        return UNET_OK;
-    } catch (const std::bad_alloc&) {
-        return UNET_ERR_NOMEM;
-    } catch (...) {
-        return UNET_ERR_INTERNAL;
-    }
 }
 
 int unet_debug_view(unet_ctx* c, int N, int H, int W, int training, int kind, int index,
