@@ -219,7 +219,7 @@ void lesion_stats_host(const void* pred, int kind, const float* targets, int N, 
                        int conn, int64_t* out);
 
 // Test-time augmentation (kernels_tta.hip; rules in tta.h): the views of x, view-major, and the
-// merge of the per-view logits.  The callers have checked the arguments (runtime.hip).
+// merge of the per-view logits.  The callers have checked the arguments (ops_abi.hip).
 int k_tta_views(const float* x, int N, int C, int H, int W, uint32_t views, float* out, hipStream_t s);
 int k_tta_merge(const float* logits, int N, int C, int H, int W, uint32_t views, int mode, float* score,
                 uint8_t* mask, uint8_t* votes, hipStream_t s);

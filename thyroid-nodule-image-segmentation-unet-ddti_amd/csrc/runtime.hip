@@ -1,7 +1,9 @@
 // Native runtime behind include/unet_hip.h: the layer graph of the reference UNets
 // (models/model.py:UNet and models/mod.py:UNet), the workspace plan (NHWC activations,
-// zero-copy concat buffers, packed weights, backward scratch) and the forward / backward /
-// optimizer orchestration on one HIP stream.  The context itself is in runtime_internal.h; the
+// zero-copy concat buffers, packed weights, backward scratch), the per-layer routes (which kernel
+// family runs each GEMM and who writes its operand image: make_routes, decided once per plan)
+// and the forward / backward / optimizer orchestration on one HIP stream, every GEMM described
+// and launched through run_rowgemm / run_wgrad.  The context itself is in runtime_internal.h; the
 // entry points that need no graph or plan (losses, metrics, augmentations) are in ops_abi.hip.
 //
 // Both reference networks are the same encoder / bottleneck / decoder topology over
@@ -326,12 +328,53 @@ void build_graph(unet_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------
+// Routes.  Which kernel family runs each GEMM of a layer and who writes its operand image,
+// decided once per plan by make_routes (below, after the rules it applies); make_plan sizes
+// the workspace from it, forward_impl and backward_impl only read it.
+// ------------------------------------------------------------------------------------
+enum Family : uint8_t {
+    FAM_NONE,   // not a GEMM: the single-input-channel first conv / first skip (k_conv_first_*,
+                // k_res_first_*)
+    FAM_REG,    // the f32 kernels, or in bf16 math the register-staged bf16 ones (kernels_gemm.hip,
+                // kernels_gemm_pipe.hip)
+    FAM_DMA16,  // the LDS-DMA bf16 kernels rg16 / wg16 (kernels_gemm16.hip)
+    FAM_X3,     // f32 math on split bf16 operands (kernels_gemm_x3.hip)
+};
+// who writes (half of) a conv's bf16 / x3 operand image
+enum Writer : uint8_t {
+    W_PREP,   // the conv's own prep pass (prep16 / prep_x3)
+    W_CONVT,  // the ConvT forward's out16 / out3 store (the up half of a decoder's concat)
+    W_POOL,   // the max-pool (the skip half of a decoder's concat; the whole image of an encoder's)
+};
+struct Route {
+    Family fwd = FAM_NONE;    // forward GEMM
+    Family dgrad = FAM_NONE;  // input gradient (bf16: rg16_on(cout, cin), not the forward's (cin, cout))
+    Family wgrad = FAM_NONE;  // weight gradient
+    bool keep = false;        // training: the forward's operand image is kept for the weight gradient
+                              // (Plan::x16 / t16 / x3 / t3; a skip GEMM reads its block's conv image)
+    // convs on FAM_DMA16 / FAM_X3: the writers of the image's up and skip halves (a conv that
+    // reads no concat: both name the whole image)
+    Writer up = W_PREP, skip = W_PREP;
+    bool head_fuse = false;   // the last conv's dz pass recomputes `do` from the 1x1 head
+    bool pool_fuse = false;   // an encoder's second conv: ... from the max-pool backward's inputs
+};
+// (fixed arrays: a plan is made four times per training step, and unet_adamw_repack reads `x3`
+// from a record of its own, so building one allocates nothing)
+struct Routes {
+    Route conv[2 * (2 * MAX_DEPTH + 1)];  // per conv
+    Route convt[MAX_DEPTH];               // per ConvT
+    Route skip[2 * MAX_DEPTH + 1];        // per block (residual network)
+    bool x3 = false;                      // some GEMM is on FAM_X3: the plan carries pack3
+};
+
+// ------------------------------------------------------------------------------------
 // Workspace plan.  A bump allocator over the caller's buffer; the same function sizes and
 // carves it so forward and backward agree on every pointer.
 // ------------------------------------------------------------------------------------
 struct Plan {
     int N, H, W;
     int64_t P[MAX_DEPTH + 1];  // pixels per level
+    Routes rt;
     float* pack;
     float* x_nhwc;
     std::vector<float*> y;
@@ -573,7 +616,72 @@ bool convt_wg16_on(const unet_ctx* c, int cin, int cout) {
 bool x3_conv_on(const unet_ctx* c, int cin, int cout) {
     return c->opt.x3 && !c->bf16 && cin % 64 == 0 && cout % 64 == 0;
 }
-bool x3_convt_on(const unet_ctx* c, int cin, int cout) { return x3_conv_on(c, cin, cout); }
+
+// The routes of this context under its present options: the one place rg16_on, wg16_on,
+// convt_wg16_on, x3_conv_on and the convt16 / pool_fuse / head_fuse options are asked.
+// P0: pixels of level 0 (the pool_fuse kernels decode pixel indices below 2^24).
+Routes make_routes(const unet_ctx* c, bool training, int64_t P0) {
+    const int D = c->depth, NC = c->nconv();
+    Routes r;
+    // a 3x3 conv / ConvT; wg16: the LDS-DMA weight gradient applies (training keeps the image)
+    auto gemms = [&](Route& q, int cin, int cout, bool wg16) {
+        if (x3_conv_on(c, cin, cout)) {
+            q.fwd = q.dgrad = q.wgrad = FAM_X3;
+            q.keep = training;
+        } else {
+            q.fwd = rg16_on(c, cin, cout) ? FAM_DMA16 : FAM_REG;
+            q.dgrad = rg16_on(c, cout, cin) ? FAM_DMA16 : FAM_REG;
+            q.keep = training && wg16;
+            q.wgrad = q.keep ? FAM_DMA16 : FAM_REG;
+        }
+        r.x3 = r.x3 || q.fwd == FAM_X3;
+    };
+    for (int i = 0; i < NC; ++i) {
+        const ConvL& L = c->conv[i];
+        if (L.pf >= 0) gemms(r.conv[i], L.cin, L.cout, wg16_on(c, L.cin, L.cout) && rg16_on(c, L.cin, L.cout));
+    }
+    for (int k = 0; k < D; ++k) {
+        const ConvTL& T = c->convt[k];
+        gemms(r.convt[k], T.cin, T.cout, convt_wg16_on(c, T.cin, T.cout));
+    }
+    // the residual network's 1x1 skip GEMMs keep the f32 kernels in f32 math; bf16: the weight
+    // gradient on the LDS-DMA kernel where the block's first conv keeps its image
+    for (int b = 1; b <= 2 * D && c->res; ++b) {
+        const ConvL& L = c->conv[2 * b];
+        Route& q = r.skip[b];
+        q.fwd = rg16_on(c, L.cin, L.cout) ? FAM_DMA16 : FAM_REG;
+        q.dgrad = rg16_on(c, L.cout, L.cin) ? FAM_DMA16 : FAM_REG;
+        q.wgrad = r.conv[2 * b].wgrad == FAM_DMA16 ? FAM_DMA16 : FAM_REG;
+    }
+    // a dz pass that leaves no f32 dz: both backward GEMMs read its image
+    auto image_dz = [](const Route& q) {
+        return q.wgrad == FAM_X3 || (q.wgrad == FAM_DMA16 && q.dgrad == FAM_DMA16);
+    };
+    for (int b = 0; b < D && !c->res; ++b) {
+        // the max-pool stores op(pooled) as the operand image of the next encoder block's first
+        // conv: x3 always (r05), bf16 where training keeps the image (r06)
+        Route& nx = r.conv[2 * (b + 1)];
+        if (nx.fwd == FAM_X3 || nx.wgrad == FAM_DMA16) nx.up = nx.skip = W_POOL;
+        // option pool_fuse (x3 r05, bf16 r06): the encoder block's second conv recomputes its
+        // `do` in the dz pass, where that pass writes an image only
+        const ConvL& C1 = c->conv[2 * b + 1];
+        r.conv[2 * b + 1].pool_fuse = c->opt.pool_fuse && C1.cout == c->ch(b) && (P0 >> (2 * b)) < (1 << 24) &&
+                                      image_dz(r.conv[2 * b + 1]);
+        // option convt16 (training): the decoder conv at this level reads its kept image only, so
+        // the max-pool stores the skip half of the concat there and the ConvT the up half (bf16:
+        // skip-first concat, identity affine).  Not in the residual network, whose 1x1 skip GEMM
+        // reads the f32 concat as well.
+        Route& dec = r.conv[2 * (2 * D - b)];
+        if (c->opt.convt16 && dec.keep && (dec.fwd == FAM_X3 || (dec.fwd == FAM_DMA16 && c->skip_first))) {
+            dec.skip = W_POOL;
+            if (r.convt[D - 1 - b].fwd == dec.fwd) dec.up = W_CONVT;
+        }
+    }
+    // option head_fuse (x3 r05, bf16 r06), one output channel: head_bwd stores no `do`
+    r.conv[NC - 1].head_fuse = c->opt.head_fuse && !c->res && c->out_ch == 1 &&
+                               c->conv[NC - 1].cout == c->base && image_dz(r.conv[NC - 1]);
+    return r;
+}
 
 // row-GEMM tile: the tap-row halo kernel for 3x3 convs (4 = 256 x 128, one block of 8 waves per
 // CU; 6 = 128 x 64 for the 64-output GEMMs, two blocks per CU); otherwise the one-tap tiles
@@ -658,6 +766,8 @@ void use_x3(const unet_ctx* c, const Plan& p, RowGemmArgs& g, const uint16_t* im
     g.ascale = g.ashift = nullptr;
     g.arelu = 0;
     g.acoef = nullptr;
+    g.ay = nullptr;  // (the f32 dgrad's description of dz's source: no x3 kernel reads it)
+    g.lday = g.offay = 0;
     g.bt = nullptr;
     g.bt16 = w3;
     g.zero16 = p.zero16;
@@ -679,6 +789,19 @@ std::string xlabel(const char* fam, int tile, int layer) {
     return b;
 }
 
+// tile and split-K partition of conv i's / ConvT k's weight gradient (p: N, H, W, P and rt set)
+WgradCfg conv_wgrad_cfg(const unet_ctx* c, const Plan& p, int i) {
+    const ConvL& L = c->conv[i];
+    const int Hl = p.H >> L.level, Wl = p.W >> L.level;
+    return p.rt.conv[i].wgrad == FAM_X3 ? x3_wgrad_cfg(c, L.cin, 9, L.cout, 1, p.P[L.level], Wl, Hl)
+                                        : wgrad_cfg(c, L.cin, 9, L.cout, 1, p.P[L.level], c->bf16, Wl);
+}
+WgradCfg convt_wgrad_cfg(const unet_ctx* c, const Plan& p, int k) {
+    const ConvTL& T = c->convt[k];
+    return p.rt.convt[k].wgrad == FAM_X3 ? x3_wgrad_cfg(c, T.cin, 1, T.cout, 4, p.P[T.in_level])
+                                         : wgrad_cfg(c, T.cin, 1, T.cout, 4, p.P[T.in_level], c->bf16);
+}
+
 void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan& p) {
     Bump b{base};
     const int D = c->depth, NC = c->nconv();
@@ -686,6 +809,7 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
     p.H = H;
     p.W = W;
     for (int l = 0; l <= D; ++l) p.P[l] = (int64_t)N * (H >> l) * (W >> l);
+    p.rt = make_routes(c, training, p.P[0]);
     p.y.assign(NC, nullptr);
     p.ldy.assign(NC, 0);
     p.offy.assign(NC, 0);
@@ -768,14 +892,13 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
         if (c->res) p.r16 = b.take<uint16_t>(n16);
     }
     p.x16.assign(NC, nullptr);
-    for (int i = 0; i < NC && training; ++i)
-        if (wg16_on(c, c->conv[i].cin, c->conv[i].cout) && rg16_on(c, c->conv[i].cin, c->conv[i].cout))
+    for (int i = 0; i < NC; ++i)
+        if (p.rt.conv[i].wgrad == FAM_DMA16)
             p.x16[i] = b.take<uint16_t>(p.P[c->conv[i].level] * c->conv[i].cin);
     p.t16.assign(c->convt.size(), nullptr);
-    for (size_t k = 0; k < c->convt.size() && training; ++k) {
+    for (size_t k = 0; k < c->convt.size(); ++k) {
         const ConvTL& T = c->convt[k];
-        if (convt_wg16_on(c, T.cin, T.cout))
-            p.t16[k] = b.take<uint16_t>(p.P[T.in_level] * T.cin);
+        if (p.rt.convt[k].wgrad == FAM_DMA16) p.t16[k] = b.take<uint16_t>(p.P[T.in_level] * T.cin);
     }
     // option x3: weight images, kept input images, one scratch image (dz, the concat
     // gradient's up half, and every input image of an inference pass)
@@ -786,17 +909,17 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
         int64_t n3 = 0;
         for (int i = 0; i < NC; ++i) {
             const ConvL& L = c->conv[i];
-            if (L.pf < 0 || !x3_conv_on(c, L.cin, L.cout)) continue;
+            if (p.rt.conv[i].fwd != FAM_X3) continue;
             n3 = std::max(n3, p.P[L.level] * std::max(L.cin, L.cout));
-            if (training) p.x3[i] = b.take<uint16_t>(3 * p.P[L.level] * L.cin);
+            if (p.rt.conv[i].keep) p.x3[i] = b.take<uint16_t>(3 * p.P[L.level] * L.cin);
         }
         for (size_t k = 0; k < c->convt.size(); ++k) {
             const ConvTL& T = c->convt[k];
-            if (!x3_convt_on(c, T.cin, T.cout)) continue;
+            if (p.rt.convt[k].fwd != FAM_X3) continue;
             n3 = std::max(n3, std::max(p.P[T.in_level] * T.cin, p.P[T.in_level - 1] * T.cout));
-            if (training) p.t3[k] = b.take<uint16_t>(3 * p.P[T.in_level] * T.cin);
+            if (p.rt.convt[k].keep) p.t3[k] = b.take<uint16_t>(3 * p.P[T.in_level] * T.cin);
         }
-        if (n3) {
+        if (p.rt.x3) {
             p.pack3 = b.take<uint16_t>(3 * c->pack_floats);
             p.s3 = b.take<uint16_t>(3 * n3);
         }
@@ -814,9 +937,7 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
         int64_t smax = 0, bmax = 0;
         for (int i = 1; i < NC; ++i) {
             const ConvL& L = c->conv[i];
-            WgradCfg w = x3_conv_on(c, L.cin, L.cout)
-                             ? x3_wgrad_cfg(c, L.cin, 9, L.cout, 1, p.P[L.level], W >> L.level, H >> L.level)
-                             : wgrad_cfg(c, L.cin, 9, L.cout, 1, p.P[L.level], c->bf16, W >> L.level);
+            const WgradCfg w = conv_wgrad_cfg(c, p, i);
             smax = std::max(smax, (int64_t)w.splits * 9 * L.cin * L.cout);
             bmax = std::max(bmax, (int64_t)w.splits * L.cout);
         }
@@ -825,10 +946,9 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
             WgradCfg w = wgrad_cfg(c, L.cin, 1, L.cout, 1, p.P[L.level], c->bf16);
             smax = std::max(smax, (int64_t)w.splits * L.cin * L.cout);
         }
-        for (const ConvTL& T : c->convt) {
-            WgradCfg w = x3_convt_on(c, T.cin, T.cout)
-                             ? x3_wgrad_cfg(c, T.cin, 1, T.cout, 4, p.P[T.in_level])
-                             : wgrad_cfg(c, T.cin, 1, T.cout, 4, p.P[T.in_level], c->bf16);
+        for (size_t k = 0; k < c->convt.size(); ++k) {
+            const ConvTL& T = c->convt[k];
+            const WgradCfg w = convt_wgrad_cfg(c, p, (int)k);
             smax = std::max(smax, (int64_t)w.splits * T.cin * 4 * T.cout);
             bmax = std::max(bmax, (int64_t)w.splits * 4 * T.cout);
         }
@@ -955,6 +1075,15 @@ Operand conv_input(unet_ctx* c, Plan& p, int i) {
     return {nullptr, 0, 0, nullptr, nullptr, 0};  // conv 0: x
 }
 
+// Input operand of ConvT k: the second conv of the bottleneck / decoder block D + k, or the
+// block's materialised output (residual network)
+Operand convt_input(const unet_ctx* c, const Plan& p, int k) {
+    const int b = c->depth + k, src = 2 * b + 1;
+    if (c->res) return {p.out[b], p.ldout[b], p.offout[b], nullptr, nullptr, 0};
+    return {p.y[src], p.ldy[src], p.offy[src], p.scale[src], p.shift[src],
+            c->bn_relu ? c->convt[k].cin : 0};
+}
+
 // BN partial rows a row GEMM emits: one per 128-row group, whatever its tile (gemm_common.h
 // row_epilogue), so the BN statistics do not depend on the tile choice
 int bn_groups(int64_t M) { return (int)((M + 127) / 128); }
@@ -983,9 +1112,9 @@ std::string tlabel16(const char* fam, int tile, int layer) {
              bm, bn, st, layer);
     return b;
 }
-// point g's A operand at the prepared bf16 image (lda = C channels)
-void use_a16(const unet_ctx* c, const Plan& p, RowGemmArgs& g, int C) {
-    g.a16 = p.s16;
+// point g's A operand at the prepared bf16 image `img` (lda = C channels)
+void use_a16(const unet_ctx* c, const Plan& p, RowGemmArgs& g, const uint16_t* img, int C) {
+    g.a16 = img;
     g.lda = C;
     g.aoff = 0;
     g.ascale = g.ashift = nullptr;
@@ -1038,13 +1167,8 @@ bool build_pack_jobs(const unet_ctx* c, bool dgrad, PackJobs& jobs) {
 }
 
 // whether the plan of this context carries x3 weight images (make_plan's pack3)
-bool plan_has_pack3(const unet_ctx* c) {
-    for (const ConvL& L : c->conv)
-        if (L.pf >= 0 && x3_conv_on(c, L.cin, L.cout)) return true;
-    for (const ConvTL& T : c->convt)
-        if (x3_convt_on(c, T.cin, T.cout)) return true;
-    return false;
-}
+// (which GEMMs run x3 depends on neither `training` nor the pixel count: any values do)
+bool plan_has_pack3(const unet_ctx* c) { return make_routes(c, true, 0).x3; }
 
 // the record of the training forward on workspace `ws` (the latest one: a workspace is reused)
 unet_ctx::FwdRec* find_fwd(unet_ctx* c, const void* ws) {
@@ -1075,10 +1199,167 @@ bool ranges_overlap(const float* a, int64_t na, const float* b, int64_t nb) {
     return na > 0 && nb > 0 && a0 < b0 + 4 * (uint64_t)nb && b0 < a0 + 4 * (uint64_t)na;
 }
 
+// ------------------------------------------------------------------------------------
+// Describing and launching a GEMM.  A site fills RowGemmArgs / WgradArgs as the f32 /
+// register-staged kernels read them and names the image where its family (Route) reads one;
+// run_rowgemm / run_wgrad switch the operands over, pick the tile and label and launch.
+// ------------------------------------------------------------------------------------
+// what the launch helpers of one forward / backward pass share
+struct Pass {
+    unet_ctx* c;
+    Plan& p;
+    Launcher L;
+};
+
+// a row GEMM over the pixels of `level`
+RowGemmArgs rowgemm_at(const Plan& p, int level, int N, int K) {
+    RowGemmArgs g{};
+    g.zero16 = p.zero16;
+    g.H = p.H >> level;
+    g.W = p.W >> level;
+    g.M = (int)p.P[level];
+    g.N = N;
+    g.K = K;
+    return g;
+}
+
+// a weight gradient over the pixels of `level`, split as wc says
+WgradArgs wgrad_at(const unet_ctx* c, const Plan& p, int level, const WgradCfg& wc) {
+    WgradArgs w{};
+    w.H = p.H >> level;
+    w.W = p.W >> level;
+    w.P = (int)p.P[level];
+    w.pps = wc.pps;
+    w.splits = wc.splits;
+    w.slab = p.slab;
+    w.bf16 = c->bf16;
+    return w;
+}
+
+// A (row GEMM) / A' (weight gradient) = op(a)
+template <class Args>
+void set_operand(Args& g, const Operand& a) {
+    g.a = a.ptr;
+    g.lda = a.ld;
+    g.aoff = a.off;
+    g.ascale = a.scale;
+    g.ashift = a.shift;
+    g.arelu = a.relu;
+}
+
+// dgrad epilogue: the result is the `do` of BN layer j, so the store also emits that layer's
+// partials (masked first by the ReLU after the BN in BN -> ReLU order)
+void bn_epilogue(const unet_ctx* c, const Plan& p, RowGemmArgs& g, int j) {
+    g.emode = E_STORE_BN;
+    g.ey = p.y[j];
+    g.ldey = p.ldy[j];
+    g.offey = p.offy[j];
+    if (c->bn_relu) {
+        g.escale = p.scale[j];
+        g.eshift = p.shift[j];
+    }
+    g.stats = p.part;
+}
+
+// the scratch image of a family (dz, the concat gradient's up half, an inference pass's inputs)
+uint16_t* scratch_image(const Plan& p, Family fam) { return fam == FAM_X3 ? p.s3 : p.s16; }
+
+// the operand image conv i's forward GEMM reads: the one kept for its weight gradient, else
+// scratch (residual network, bf16: the block's first conv shares its image with the skip GEMM,
+// which runs after the second conv has reused the scratch image)
+uint16_t* conv_image(const unet_ctx* c, const Plan& p, int i) {
+    if (p.rt.conv[i].fwd == FAM_X3) return p.x3[i] ? p.x3[i] : p.s3;
+    return p.x16[i] ? p.x16[i] : (c->res && c->conv[i].which == 0) ? p.r16 : p.s16;
+}
+
+// channels [coff, coff + n) of op(a) into the bf16 / x3 image img ([M][ld]) at the same offset
+int prep_image(Launcher& L, Family fam, const Operand& a, int coff, int n, int64_t M, uint16_t* img,
+               int ld) {
+    const float* sc = a.scale ? a.scale + coff : nullptr;
+    const float* sh = a.shift ? a.shift + coff : nullptr;
+    const int relu = std::min(std::max(a.relu - coff, 0), n);
+    if (fam == FAM_X3)
+        RUN("prep_x3", 0, k_to_x3(a.ptr, a.ld, a.off + coff, n, sc, sh, relu, M, img, ld, coff, L.s));
+    else
+        RUN("prep16", 0, k_to_bf16(a.ptr, a.ld, a.off + coff, n, sc, sh, relu, M, img + coff, L.s, ld));
+    return 0;
+}
+
+// the weight gradient reads images instead: A' = the forward's kept image `img` ([pixels][CA]),
+// B' = the family's scratch image ([pixels][CB])
+void use_images(const unet_ctx* c, const Plan& p, WgradArgs& w, Family fam, const uint16_t* img) {
+    w.a = (const float*)img;
+    w.lda = w.CA;
+    w.aoff = 0;
+    w.ascale = w.ashift = nullptr;
+    w.arelu = 0;
+    w.b = (const float*)scratch_image(p, fam);
+    w.ldb = w.CB;
+    w.boff = 0;
+    w.by = nullptr;
+    w.bcoef = nullptr;
+    w.zero16 = p.zero16;
+    w.xcd = fam == FAM_X3 ? 1 : xcd16_on(c);
+}
+
+// One row GEMM of family `fam`.  g: the GEMM as the f32 / register-staged kernel reads it, and
+// in g.a16 the prepared image ([pixels][g.C]) the other two families read instead.  wimg: the
+// weight image in the pack region (f32, or bf16 in the same slot; the x3 copy of the region
+// holds its x3 image at 3x the offset), or the 1x1 skip parameter itself.
+int run_rowgemm(Pass& ps, const char* site, int layer, double flop, Family fam, bool dgrad,
+                const float* wimg, RowGemmArgs& g) {
+    unet_ctx* c = ps.c;
+    Launcher& L = ps.L;
+    if (fam == FAM_X3) {
+        use_x3(c, ps.p, g, g.a16, g.C, ps.p.pack3 + 3 * (wimg - ps.p.pack));
+        const int tile = x3_tile(c, g);
+        RUN(xlabel(site, tile, layer), flop, launch_rowgemm_x3(g, tile, L.s));
+        return 0;
+    }
+    set_weights(c, g, wimg);
+    if (fam == FAM_DMA16) {
+        use_a16(c, ps.p, g, g.a16, g.C);
+        const int tile = rg16_tile(c, g);
+        RUN(tlabel16(site, tile, layer), flop, launch_rowgemm16(g, tile, L.s));
+        return 0;
+    }
+    // pick_tile's ConvT rules.  Invariant: only the ConvT forward stores through E_CONVT (its
+    // grid N is 4 cout; the tile goes by cout) and only the ConvT input gradient gathers through
+    // G_UP2.  A new GEMM with either mode that is no ConvT needs its own flag here.
+    const bool convt = g.emode == E_CONVT || g.amode == G_UP2;
+    const int tile = pick_tile(c, g.emode == E_CONVT ? g.cout : g.N, dgrad, c->bf16, convt);
+    RUN(tlabel(site, tile, layer), flop, launch_rowgemm(g, tile, L.s));
+    return 0;
+}
+
+// One weight gradient of family `fam`, split as wc says.  tile16: the LDS-DMA tile where the
+// site picks it (-1 = option wg16_tile).
+int run_wgrad(Pass& ps, const char* site, int layer, double flop, Family fam, const WgradCfg& wc,
+              const WgradArgs& w, int tile16 = -1) {
+    unet_ctx* c = ps.c;
+    Launcher& L = ps.L;
+    if (fam == FAM_X3) {
+        RUN(x3wlabel(site, wc, layer), flop, launch_wgrad_x3(w, wc.tile, L.s));
+    } else if (fam == FAM_DMA16) {
+        const int t = tile16 >= 0 ? tile16 : wg16_tile(c, w.CA, w.CB);
+        int bm = 0, bn = 0, st = 0;
+        wgrad16g_tile_dims(t, &bm, &bn, &st);
+        char lb[112];
+        // (the tap-row kernels are 3x3 only)
+        snprintf(lb, sizeof lb, "%s/wg16%s_%dx%ds%d|%d", site,
+                 w.amode != G_CONV3 ? "" : t == 4 ? "r3" : t == 7 ? "r3m" : "", bm, bn, st, layer);
+        RUN(lb, flop, launch_wgrad16(w, t, L.s));
+    } else {
+        RUN(wlabel(site, wc, layer), flop, launch_wgrad(w, wc.tile, L.s));
+    }
+    return 0;
+}
+
 // rec: this training forward's record (nullptr: an eval forward, no backward follows)
 int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, const float* x,
                  float* logits, Plan& p, bool training, unet_ctx::FwdRec* rec, hipStream_t s) {
-    Launcher L{c, s};
+    Pass ps{c, p, Launcher{c, s}};
+    Launcher& L = ps.L;
     const int H = p.H, W = p.W, D = c->depth, NC = c->nconv();
     // 1. weight images for the row GEMMs: re-packed every call (params may have changed through
     //    the optimizer or load_state_dict; ~0.1 ms of HBM traffic per step at config 2) unless
@@ -1120,203 +1401,91 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
     RUN("copy_x", 0, (int)hipMemcpyAsync(p.x_nhwc, x, sizeof(float) * p.P[0] * c->in_ch,
                                          hipMemcpyDeviceToDevice, s));
     const float* xin = p.x_nhwc;
-    // decoder convs whose operand image already holds the ConvT's up half (option convt16)
-    std::vector<char> up16(NC, 0);
-    // x3: the max-pool wrote the next encoder conv's x3 operand image itself (no f32 pooled
-    // tensor, no prep pass; r05)
-    std::vector<char> pool3(NC, 0);
-    // (r06) bf16: the max-pool wrote the next encoder conv's bf16 operand image (pool16); both
-    // paths: the max-pool wrote the decoder conv's skip half of its kept image (skipimg)
-    std::vector<char> pool16(NC, 0), skipimg(NC, 0);
 
     auto conv = [&](int i) -> int {
         const ConvL& C = c->conv[i];
-        const int Hl = H >> C.level, Wl = W >> C.level;
+        const Route& rt = p.rt.conv[i];
         const int64_t M = p.P[C.level];
-        int R;
-        if (i == 0 && C.pf < 0) {
-            R = wide_g(M);
+        if (rt.fwd == FAM_NONE) {
+            const int R = wide_g(M);
             RUN("conv_first_fwd", 2.0 * M * 9 * C.cout,
-                k_conv_first_fwd(xin, prm + C.w, bias_ptr(prm, C.b), p.y[0], (int)M, Hl, Wl, C.cout,
-                                 c->bn_relu ? 0 : 1, p.stats, R, s));
-        } else {
-            Operand a = conv_input(c, p, i);
-            RowGemmArgs g{};
-            g.zero16 = p.zero16;
-            g.H = Hl;
-            g.W = Wl;
-            g.M = (int)M;
-            g.N = C.cout;
-            g.K = 9 * C.cin;
-            g.a = a.ptr;
-            g.lda = a.ld;
-            g.aoff = a.off;
-            g.C = C.cin;
-            g.amode = G_CONV3;
-            g.ascale = a.scale;
-            g.ashift = a.shift;
-            g.arelu = a.relu;
-            set_weights(c, g, p.pack + C.pf);
-            g.out = p.y[i];
-            g.ldo = p.ldy[i];
-            g.ooff = p.offy[i];
-            g.bias = bias_ptr(prm, C.b);
-            g.stats = p.stats;
-            g.emode = c->bn_relu ? E_STATS : E_BIAS_RELU_STATS;
-            if (p.pack3 && x3_conv_on(c, C.cin, C.cout)) {
-                uint16_t* img = p.x3[i] ? p.x3[i] : p.s3;
-                if (pool3[i]) {
-                    // (the max-pool already stored op(pooled) as this conv's x3 image)
-                } else if (up16[i] && skipimg[i]) {
-                    // (the ConvT stored the up half, the max-pool the skip half)
-                } else if (up16[i]) {  // the ConvT stored the up half's x3 split: convert the skip half
-                    const int l = C.level, so = c->skip_off(l), ch = c->ch(l);
-                    const int rl = std::min(std::max(a.relu - so, 0), ch);
-                    RUN("prep_x3", 0, k_to_x3(a.ptr, a.ld, a.off + so, ch, a.scale ? a.scale + so : nullptr,
-                                              a.shift ? a.shift + so : nullptr, rl, M, img, C.cin, so, s));
-                } else {
-                    RUN("prep_x3", 0, k_to_x3(a.ptr, a.ld, a.off, C.cin, a.scale, a.shift, a.relu, M, img,
-                                              C.cin, 0, s));
-                }
-                use_x3(c, p, g, img, C.cin, p.pack3 + 3 * C.pf);
-                const int tile = x3_tile(c, g);
-                R = bn_groups(M);
-                RUN(xlabel("conv_fwd", tile, i), 2.0 * M * C.cout * 9 * C.cin, launch_rowgemm_x3(g, tile, s));
-                return stats_finalize(c, L, p, i, R, M, training, prm, bn_run, bn_cnt);
-            }
-            if (rg16_on(c, C.cin, C.cout)) {
-                // (residual network: the block's first conv shares its image with the skip GEMM,
-                // which runs after the second conv has reused the scratch image)
-                uint16_t* img = p.x16[i] ? p.x16[i] : (c->res && C.which == 0) ? p.r16 : p.s16;
-                if (pool16[i] || (up16[i] && skipimg[i])) {
-                    // (the max-pool / the ConvT and the max-pool stored the whole image)
-                } else if (up16[i]) {  // the ConvT stored the up half already: convert the skip half
-                    const int l = C.level, so = c->skip_off(l);
-                    RUN("prep16", 0, k_to_bf16(a.ptr, a.ld, a.off + so, c->ch(l), a.scale + so,
-                                               a.shift + so, a.relu, M, img + so, s, C.cin));
-                } else {
-                    RUN("prep16", 0, k_to_bf16(a.ptr, a.ld, a.off, C.cin, a.scale, a.shift, a.relu, M,
-                                               img, s));
-                }
-                use_a16(c, p, g, C.cin);
-                g.a16 = img;
-                const int tile = rg16_tile(c, g);
-                R = bn_groups(M);
-                RUN(tlabel16("conv_fwd", tile, i), 2.0 * M * C.cout * 9 * C.cin, launch_rowgemm16(g, tile, s));
-                return stats_finalize(c, L, p, i, R, M, training, prm, bn_run, bn_cnt);
-            }
-            R = bn_groups(M);
-            const int tile = pick_tile(c, C.cout, false, c->bf16);
-            RUN(tlabel("conv_fwd", tile, i), 2.0 * M * C.cout * 9 * C.cin, launch_rowgemm(g, tile, s));
+                k_conv_first_fwd(xin, prm + C.w, bias_ptr(prm, C.b), p.y[0], (int)M, H >> C.level,
+                                 W >> C.level, C.cout, c->bn_relu ? 0 : 1, p.stats, R, s));
+            return stats_finalize(c, L, p, i, R, M, training, prm, bn_run, bn_cnt);
         }
-        return stats_finalize(c, L, p, i, R, M, training, prm, bn_run, bn_cnt);
+        const Operand a = conv_input(c, p, i);
+        RowGemmArgs g = rowgemm_at(p, C.level, C.cout, 9 * C.cin);
+        set_operand(g, a);
+        g.C = C.cin;
+        g.amode = G_CONV3;
+        g.out = p.y[i];
+        g.ldo = p.ldy[i];
+        g.ooff = p.offy[i];
+        g.bias = bias_ptr(prm, C.b);
+        g.stats = p.stats;
+        g.emode = c->bn_relu ? E_STATS : E_BIAS_RELU_STATS;
+        if (rt.fwd != FAM_REG) {
+            uint16_t* img = conv_image(c, p, i);
+            if (rt.up == W_PREP) {  // the whole image (over a skip half the max-pool may have stored)
+                if (int rc = prep_image(L, rt.fwd, a, 0, C.cin, M, img, C.cin)) return rc;
+            } else if (rt.skip == W_PREP) {  // the ConvT stored the up half: convert the skip half
+                if (int rc = prep_image(L, rt.fwd, a, c->skip_off(C.level), c->ch(C.level), M, img, C.cin))
+                    return rc;
+            }  // (else the max-pool, or the ConvT and the max-pool, stored the whole image)
+            g.a16 = img;
+        }
+        if (int rc = run_rowgemm(ps, "conv_fwd", i, 2.0 * M * C.cout * 9 * C.cin, rt.fwd, false,
+                                 p.pack + C.pf, g))
+            return rc;
+        return stats_finalize(c, L, p, i, bn_groups(M), M, training, prm, bn_run, bn_cnt);
     };
     auto convT = [&](int k) -> int {
         const ConvTL& T = c->convt[k];
-        const int src = 2 * (D + k) + 1;  // second conv of the bottleneck / decoder block
+        const Route& rt = p.rt.convt[k];
         const int lo = T.in_level - 1;
-        RowGemmArgs g{};
-        g.zero16 = p.zero16;
-        g.H = H >> T.in_level;
-        g.W = W >> T.in_level;
-        g.M = (int)p.P[T.in_level];
-        g.N = 4 * T.cout;
-        g.K = T.cin;
-        if (c->res) {  // the materialised output of block D+k
-            g.a = p.out[D + k];
-            g.lda = p.ldout[D + k];
-            g.aoff = p.offout[D + k];
-        } else {
-            g.a = p.y[src];
-            g.lda = p.ldy[src];
-            g.aoff = p.offy[src];
-            g.ascale = p.scale[src];
-            g.ashift = p.shift[src];
-            g.arelu = c->bn_relu ? T.cin : 0;
-        }
+        const Operand a = convt_input(c, p, k);
+        RowGemmArgs g = rowgemm_at(p, T.in_level, 4 * T.cout, T.cin);
+        set_operand(g, a);
         g.C = T.cin;
         g.amode = G_IDENT;
-        set_weights(c, g, p.pack + T.pf);
         g.out = p.cat[lo];
         g.ldo = 2 * c->ch(lo);
         g.ooff = c->up_off(lo);
         g.bias = prm + T.b;
         g.cout = T.cout;
         g.emode = E_CONVT;
-        if (p.pack3 && x3_convt_on(c, T.cin, T.cout)) {
-            uint16_t* img = p.t3[k] ? p.t3[k] : p.s3;
-            RUN("prep_x3", 0, k_to_x3(g.a, g.lda, g.aoff, T.cin, g.ascale, g.ashift, g.arelu, g.M, img,
-                                      T.cin, 0, s));
-            use_x3(c, p, g, img, T.cin, p.pack3 + 3 * T.pf);
-            // option convt16 (x3 training): the up half of the decoder's concat goes straight
-            // into that conv's kept x3 image, its only reader; the conv's prep pass then
-            // converts the skip half only
-            const int idec = 2 * (D + 1 + k);
-            const ConvL& Cd = c->conv[idec];
-            // (not in the residual network: its 1x1 skip GEMM reads the f32 concat as well)
-            if (c->opt.convt16 && !c->res && p.x3[idec] && x3_conv_on(c, Cd.cin, Cd.cout)) {
-                g.out3 = p.x3[idec];
-                up16[idec] = true;
-            }
-            const int tile = x3_tile(c, g);
-            RUN(xlabel("convT_fwd", tile, 100 + k), 2.0 * g.M * g.N * g.K, launch_rowgemm_x3(g, tile, s));
-            return 0;
-        }
-        if (rg16_on(c, T.cin, T.cout)) {
-            uint16_t* img = p.t16[k] ? p.t16[k] : p.s16;
-            RUN("prep16", 0, k_to_bf16(g.a, g.lda, g.aoff, T.cin, g.ascale, g.ashift, g.arelu, g.M,
-                                       img, s));
-            use_a16(c, p, g, T.cin);
+        if (rt.fwd != FAM_REG) {
+            const bool x3 = rt.fwd == FAM_X3;
+            uint16_t* kept = x3 ? p.t3[k] : p.t16[k];
+            uint16_t* img = kept ? kept : x3 ? p.s3 : p.s16;
+            if (int rc = prep_image(L, rt.fwd, a, 0, T.cin, g.M, img, T.cin)) return rc;
             g.a16 = img;
-            // option convt16: the up half goes to the decoder conv's kept bf16 image (the only
-            // reader of that half in a bf16 training step; skip-first concat, identity affine)
+            // option convt16 (training): the up half of the decoder's concat goes straight into
+            // that conv's kept operand image, its only reader (identity affine); the conv's prep
+            // pass then converts the skip half only, or nothing where the max-pool stored it
             const int idec = 2 * (D + 1 + k);
-            const ConvL& Cd = c->conv[idec];
-            // (not in the residual network: its max-pool does not write the skip half of that
-            // image)
-            if (c->opt.convt16 && !c->res && c->skip_first && p.x16[idec] && rg16_on(c, Cd.cin, Cd.cout)) {
-                g.out16 = p.x16[idec];
-                up16[idec] = true;
-            }
-            const int tile = rg16_tile(c, g);
-            RUN(tlabel16("convT_fwd", tile, 100 + k), 2.0 * g.M * g.N * g.K,
-                launch_rowgemm16(g, tile, s));
-            return 0;
+            if (p.rt.conv[idec].up == W_CONVT) (x3 ? g.out3 : g.out16) = conv_image(c, p, idec);
         }
-        const int tile = pick_tile(c, T.cout, false, c->bf16, true);  // grid N = 4 cout
-        RUN(tlabel("convT_fwd", tile, 100 + k), 2.0 * g.M * g.N * g.K, launch_rowgemm(g, tile, s));
-        return 0;
+        return run_rowgemm(ps, "convT_fwd", 100 + k, 2.0 * g.M * g.N * g.K, rt.fwd, false,
+                           p.pack + T.pf, g);
     };
 
     // residual block b closes with out = ReLU(BN2(z2) + skip(x)) (mod.py:86)
     auto block_out = [&](int b) -> int {
         const ConvL& CL = c->conv[2 * b];
+        const Route& rt = p.rt.skip[b];
         const int i2 = 2 * b + 1;
         const int64_t M = p.P[CL.level];
-        if (CL.pf < 0) {  // Cin = 1: the skip is a per-channel scale of the image
+        if (rt.fwd == FAM_NONE) {  // Cin = 1: the skip is a per-channel scale of the image
             RUN("res_out", 0, k_res_first_fwd(xin, prm + c->skip_w[b], p.y[i2], p.scale[i2],
                                               p.shift[i2], M, CL.cout, p.out[b], p.ldout[b],
                                               p.offout[b], s));
             return 0;
         }
-        Operand a = conv_input(c, p, 2 * b);
-        RowGemmArgs g{};
-        g.zero16 = p.zero16;
-        g.H = H >> CL.level;
-        g.W = W >> CL.level;
-        g.M = (int)M;
-        g.N = CL.cout;
-        g.K = CL.cin;
-        g.a = a.ptr;
-        g.lda = a.ld;
-        g.aoff = a.off;
+        RowGemmArgs g = rowgemm_at(p, CL.level, CL.cout, CL.cin);
+        set_operand(g, conv_input(c, p, 2 * b));
         g.C = CL.cin;
         g.amode = G_IDENT;
-        if (c->bf16)
-            g.bt16 = (const uint16_t*)(p.pack + c->skip_pf[b]);
-        else
-            g.bt = prm + c->skip_w[b];  // torch layout [co][ci] is already Bt[n][k]
-        g.xcd = xcd_remap_on(c);
         g.out = p.out[b];
         g.ldo = p.ldout[b];
         g.ooff = p.offout[b];
@@ -1326,16 +1495,11 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
         g.offey = p.offy[i2];
         g.escale = p.scale[i2];
         g.eshift = p.shift[i2];
-        if (rg16_on(c, CL.cin, CL.cout)) {  // from the image conv1 read: rounded once, read twice
-            use_a16(c, p, g, CL.cin);
-            g.a16 = p.x16[2 * b] ? p.x16[2 * b] : p.r16;
-            const int tile = rg16_tile(c, g);
-            RUN(tlabel16("skip_fwd", tile, b), 2.0 * M * CL.cout * CL.cin, launch_rowgemm16(g, tile, s));
-            return 0;
-        }
-        const int tile = pick_tile(c, CL.cout, false, c->bf16);
-        RUN(tlabel("skip_fwd", tile, b), 2.0 * M * CL.cout * CL.cin, launch_rowgemm(g, tile, s));
-        return 0;
+        // LDS-DMA: from the image conv1 read (rounded once, read twice)
+        if (rt.fwd == FAM_DMA16) g.a16 = conv_image(c, p, 2 * b);
+        // (f32: the torch layout [co][ci] of the parameter is already Bt[n][k])
+        return run_rowgemm(ps, "skip_fwd", b, 2.0 * M * CL.cout * CL.cin, rt.fwd, false,
+                           c->bf16 ? p.pack + c->skip_pf[b] : prm + c->skip_w[b], g);
     };
 
     int rc;
@@ -1350,33 +1514,21 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
                     k_maxpool_bn(p.out[b], p.ldout[b], p.offout[b], nullptr, nullptr, 0, p.N, H >> b,
                                  W >> b, C, p.pool[b], p.idx[b], s));
             else {
-                const int j = 2 * (b + 1);  // the next encoder block's first conv
-                const ConvL& Cj = c->conv[j];
-                uint16_t* out3 = nullptr;
-                uint16_t *o16 = nullptr, *s16 = nullptr, *s3 = nullptr;
-                if (p.pack3 && x3_conv_on(c, Cj.cin, Cj.cout)) {
-                    out3 = p.x3[j] ? p.x3[j] : p.s3;
-                    pool3[j] = 1;
-                } else if (p.x16[j] && rg16_on(c, Cj.cin, Cj.cout)) {  // (r06) training, bf16
-                    o16 = p.x16[j];
-                    pool16[j] = 1;
-                }
+                // x3 (r05) / bf16 training (r06): op(pooled) straight into the operand image of the
+                // next encoder block's first conv (no f32 pooled tensor, no prep pass)
+                const int j = 2 * (b + 1);
+                uint16_t *out3 = nullptr, *o16 = nullptr, *s16 = nullptr, *s3 = nullptr;
+                if (p.rt.conv[j].up == W_POOL) (p.rt.conv[j].fwd == FAM_X3 ? out3 : o16) = conv_image(c, p, j);
                 // (r06) the skip half of the decoder conv at this level (its ConvT stores the
                 // up half, option convt16): op(BN(y)) as that conv's kept operand image
                 const int idec = 2 * (2 * D - b);
-                const ConvL& Cd = c->conv[idec];
-                if (c->opt.convt16) {
-                    if (p.pack3 && p.x3[idec] && x3_conv_on(c, Cd.cin, Cd.cout))
-                        s3 = p.x3[idec];
-                    else if (c->bf16 && c->skip_first && p.x16[idec] && rg16_on(c, Cd.cin, Cd.cout))
-                        s16 = p.x16[idec];
-                }
-                skipimg[idec] = s3 || s16;
+                if (p.rt.conv[idec].skip == W_POOL)
+                    (p.rt.conv[idec].fwd == FAM_X3 ? s3 : s16) = conv_image(c, p, idec);
                 RUN("maxpool_fwd", 0,
                     k_maxpool_bn(p.y[i], p.ldy[i], p.offy[i], p.scale[i], p.shift[i],
                                  c->bn_relu ? 1 : 0, p.N, H >> b, W >> b, C,
                                  out3 || o16 ? nullptr : p.pool[b],  // (its images are the only readers)
-                                 p.idx[b], s, out3, o16, s16, s3, Cd.cin, c->skip_off(b)));
+                                 p.idx[b], s, out3, o16, s16, s3, c->conv[idec].cin, c->skip_off(b)));
             }
         }
     }
@@ -1401,7 +1553,8 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
 
 int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* grads, Plan& p,
                   hipStream_t s) {
-    Launcher L{c, s};
+    Pass ps{c, p, Launcher{c, s}};
+    Launcher& L = ps.L;
     const int H = p.H, W = p.W, D = c->depth, NC = c->nconv();
     int rc;
     // (weight gradients run on the same stream as the dgrad chain: a second stream measured
@@ -1429,12 +1582,9 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
     // dz = A do + B (y - mean) + C as one elementwise pass over do, or (option dz_in_wgrad)
     // inside the weight gradient's B' loader, which also stores it for the dgrad
     const int dz_mask = c->bn_relu ? 0 : 1;
-    // conv whose x3 dz pass recomputes `do` from the 1x1 head (set below when it applies)
-    int head_src_conv = -1;
-    // conv whose x3 dz pass recomputes `do` from the max-pool backward's inputs (option
-    // pool_fuse, r05): the encoder block's second conv
+    // what the dz pass of an encoder block's second conv recomputes its `do` from where the
+    // route says pool_fuse (r05): the max-pool backward's inputs
     struct PoolSrc {
-        int conv = -1;
         const float* dp = nullptr;
         const uint8_t* idx = nullptr;
         const float* dskip = nullptr;
@@ -1447,27 +1597,39 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
     auto conv_bwd = [&](int i, const float* dout, float* dx, int ldx, bool bn_next,
                         int* rows, bool accumulate = false) -> int {
         const ConvL& C = c->conv[i];
+        const Route& rt = p.rt.conv[i];
         const int Hl = H >> C.level, Wl = W >> C.level;
         const int64_t P = p.P[C.level];
-        if (i == 0 && C.pf < 0) {
+        const double flop = 2.0 * P * C.cout * 9 * C.cin;
+        if (rt.wgrad == FAM_NONE) {
             RUN("conv_first_wgrad", 2.0 * P * 9 * C.cout,
                 k_conv_first_wgrad(p.x_nhwc, dout, p.y[0], p.coef, (int)P, Hl, Wl, C.cout, dz_mask,
                                    p.hpart, wide_g(P), grads + C.w,
                                    C.b >= 0 ? grads + C.b : nullptr, s));
             return 0;
         }
-        if (p.pack3 && x3_conv_on(c, C.cin, C.cout)) {
+        const WgradCfg wc = conv_wgrad_cfg(c, p, i);
+        WgradArgs w = wgrad_at(c, p, C.level, wc);
+        w.CA = C.cin;
+        w.amode = G_CONV3;
+        w.CB = C.cout;
+        w.bmode = G_IDENT;
+        w.Mw = 9 * C.cin;
+        w.Nw = C.cout;
+        bool dzw = false;
+        int t16 = -1;
+        if (rt.wgrad == FAM_X3) {
             // option x3: dz as an x3 image (and the conv bias's column partials), the weight
             // gradient from the forward's kept input image and dz, the input gradient from dz
             float* bp = C.b >= 0 ? p.part : nullptr;
-            // (r05) the last conv's `do` straight from the 1x1 head (head_bwd stored none)
-            const bool hsrc = i == head_src_conv;
-            if (i == pool_src.conv) {  // (r05) do straight from the max-pool backward's inputs
+            if (rt.pool_fuse) {  // (r05) do straight from the max-pool backward's inputs
                 const PoolSrc& q = pool_src;
                 RUN("bn_dz", 0, k_bn_dz_x3_pool(p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask, p.s3,
                                                 bp, q.dp, q.idx, q.dskip, q.ldskip, q.msc, q.msh, p.N, Hl,
                                                 Wl, s));
             } else {
+                // (r05) head_fuse: the last conv's `do` straight from the 1x1 head (head_bwd stored none)
+                const bool hsrc = rt.head_fuse;
                 RUN("bn_dz", 0, k_bn_dz_x3(dout, p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask,
                                           p.s3, bp, s, hsrc ? dlogits : nullptr,
                                           hsrc ? prm + c->head_w : nullptr, hsrc ? p.scale[i] : nullptr,
@@ -1482,382 +1644,145 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
                     RUN("bias_grad", 0, k_sum_partials(p.part, G, C.cout, grads + C.b, s));
                 }
             }
-            const WgradCfg wc = x3_wgrad_cfg(c, C.cin, 9, C.cout, 1, P, Wl, Hl);
-            WgradArgs w{};
-            w.xcd = 1;
-            w.H = Hl;
-            w.W = Wl;
-            w.P = (int)P;
-            w.a = (const float*)p.x3[i];
-            w.lda = C.cin;
-            w.CA = C.cin;
-            w.amode = G_CONV3;
-            w.b = (const float*)p.s3;
-            w.ldb = C.cout;
-            w.CB = C.cout;
-            w.bmode = G_IDENT;
-            w.Mw = 9 * C.cin;
-            w.Nw = C.cout;
-            w.pps = wc.pps;
-            w.splits = wc.splits;
-            w.slab = p.slab;
-            w.zero16 = p.zero16;
-            RUN(x3wlabel("conv_wgrad", wc, i), 2.0 * P * C.cout * 9 * C.cin, launch_wgrad_x3(w, wc.tile, s));
-            RUN("wgrad_reduce", 0,
-                k_slab_reduce(p.slab, wc.splits, w.Mw, w.Nw, 0, C.cin, C.cout, grads + C.w, s));
-            if (!dx) return 0;
-            RowGemmArgs g{};
-            g.H = Hl;
-            g.W = Wl;
-            g.M = (int)P;
-            g.N = C.cin;
-            g.K = 9 * C.cout;
-            g.C = C.cout;
-            g.amode = G_CONV3;
-            use_x3(c, p, g, p.s3, C.cout, p.pack3 + 3 * C.pd);
-            g.out = dx;
-            g.ldo = ldx;
-            g.ooff = 0;
-            g.emode = accumulate ? E_ADD : E_STORE;
-            if (bn_next) {
-                g.emode = E_STORE_BN;
-                g.ey = p.y[i - 1];
-                g.ldey = p.ldy[i - 1];
-                g.offey = p.offy[i - 1];
-                if (c->bn_relu) {
-                    g.escale = p.scale[i - 1];
-                    g.eshift = p.shift[i - 1];
+            use_images(c, p, w, FAM_X3, p.x3[i]);
+        } else {
+            // bf16 image of dz: A operand of the LDS-DMA dgrad, B' of the LDS-DMA wgrad; the f32
+            // dz is still written when the register-staged kernel of either consumes it
+            const bool wg16 = rt.wgrad == FAM_DMA16, rg16 = rt.dgrad == FAM_DMA16;
+            const bool dz16 = rg16 || wg16;
+            // option dz_in_wgrad: the weight gradient's B' loader forms dz from do and y (the
+            // bn_dz pass disappears) and its first A'-tile blocks store it for the dgrad; f32
+            // register-staged weight-gradient tiles only, with a dgrad to feed (r04: both BN orders;
+            // BN -> ReLU forms dz unmasked, do already carries the ReLU mask)
+            dzw = p.gdz && C.cin <= c->opt.dz_in_wgrad && !dz16 && dx && (wc.tile < 10 || wc.tile >= 20);
+            if (dzw) {
+            } else if (dz16) {
+                const bool f32 = !wg16 || !(dx && rg16);
+                if (rt.pool_fuse && !f32) {  // (r06) do straight from the max-pool backward's inputs
+                    const PoolSrc& q = pool_src;
+                    RUN("bn_dz", 0, k_bn_dz16_pool(p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask, p.s16,
+                                                   q.dp, q.idx, q.dskip, q.ldskip, q.msc, q.msh, p.N, Hl, Wl, s));
+                } else if (rt.pool_fuse) {
+                    return fail(c, UNET_ERR_INTERNAL, "pool_fuse: conv %d needs an f32 dz", i);
+                } else if (rt.head_fuse) {  // (r06) do straight from the 1x1 head
+                    if (f32) return fail(c, UNET_ERR_INTERNAL, "head_fuse: conv %d needs an f32 dz", i);
+                    RUN("bn_dz", 0, k_bn_dz16(nullptr, p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask,
+                                              p.s16, 0, s, dlogits, prm + c->head_w, p.scale[i], p.shift[i],
+                                              c->bn_relu ? 1 : 0));
+                } else {
+                    RUN("bn_dz", 0, k_bn_dz16(const_cast<float*>(dout), p.y[i], p.ldy[i], p.offy[i], P, C.cout,
+                                              p.coef, dz_mask, p.s16, f32 ? 1 : 0, s));
                 }
-                g.stats = p.part;
-            }
-            const int tile = x3_tile(c, g);
-            if (rows) *rows = bn_groups(P);
-            RUN(xlabel("conv_dgrad", tile, i), 2.0 * P * C.cout * 9 * C.cin, launch_rowgemm_x3(g, tile, s));
-            return 0;
-        }
-        // bf16 image of dz: A operand of the LDS-DMA dgrad, B' of the LDS-DMA wgrad; the f32
-        // dz is still written when the register-staged kernel of either consumes it
-        const bool dz16 = rg16_on(c, C.cout, C.cin) || p.x16[i];
-        Operand a = conv_input(c, p, i);
-        WgradCfg wc = wgrad_cfg(c, C.cin, 9, C.cout, 1, P, c->bf16, Wl);
-        // option dz_in_wgrad: the weight gradient's B' loader forms dz from do and y (the
-        // bn_dz pass disappears) and its first A'-tile blocks store it for the dgrad; f32
-        // register-staged weight-gradient tiles only, with a dgrad to feed (r04: both BN orders;
-        // BN -> ReLU forms dz unmasked, do already carries the ReLU mask)
-        const bool dzw = p.gdz && C.cin <= c->opt.dz_in_wgrad && !dz16 && dx &&
-                         (wc.tile < 10 || wc.tile >= 20);
-        if (dzw) {
-        } else if (dz16) {
-            const bool f32 = !p.x16[i] || !(dx && rg16_on(c, C.cout, C.cin));
-            if (i == pool_src.conv && !f32) {  // (r06) do straight from the max-pool backward's inputs
-                const PoolSrc& q = pool_src;
-                RUN("bn_dz", 0, k_bn_dz16_pool(p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask, p.s16,
-                                               q.dp, q.idx, q.dskip, q.ldskip, q.msc, q.msh, p.N, Hl, Wl, s));
-            } else if (i == pool_src.conv) {
-                return fail(c, UNET_ERR_INTERNAL, "pool_fuse: conv %d needs an f32 dz", i);
-            } else if (i == head_src_conv) {  // (r06) do straight from the 1x1 head
-                if (f32) return fail(c, UNET_ERR_INTERNAL, "head_fuse: conv %d needs an f32 dz", i);
-                RUN("bn_dz", 0, k_bn_dz16(nullptr, p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask,
-                                          p.s16, 0, s, dlogits, prm + c->head_w, p.scale[i], p.shift[i],
-                                          c->bn_relu ? 1 : 0));
             } else {
-                RUN("bn_dz", 0, k_bn_dz16(const_cast<float*>(dout), p.y[i], p.ldy[i], p.offy[i], P, C.cout,
-                                          p.coef, dz_mask, p.s16, f32 ? 1 : 0, s));
+                RUN("bn_dz", 0, k_bn_dz(const_cast<float*>(dout), p.y[i], p.ldy[i], p.offy[i], P, C.cout,
+                                        p.coef, dz_mask, s));
             }
-        } else {
-            RUN("bn_dz", 0, k_bn_dz(const_cast<float*>(dout), p.y[i], p.ldy[i], p.offy[i], P, C.cout,
-                                    p.coef, dz_mask, s));
+            w.xcd = xcd_remap_wgrad(c);
+            set_operand(w, conv_input(c, p, i));
+            w.b = dout;
+            w.ldb = C.cout;
+            w.by = p.y[i];
+            w.ldby = p.ldy[i];
+            w.offby = p.offy[i];
+            w.bcoef = dzw ? p.coef : nullptr;
+            w.dzout = dzw ? p.gdz : nullptr;
+            w.bdznomask = dz_mask ? 0 : 1;
+            w.lddz = C.cout;
+            w.bias_slab = C.b >= 0 ? p.bslab : nullptr;
+            if (wg16) {
+                use_images(c, p, w, FAM_DMA16, p.x16[i]);
+                // (the split count, sized for >= 2048 128x128 tiles, gives >= 512 256x256 ones)
+                t16 = wg16_tile(c, C.cin, C.cout);
+                // option wg16_r3: the tap-row kernel (three taps per block from one halo row)
+                const int r3 = c->opt.wg16_r3;
+                // (r06) tile 7 also at W = 32 / 16 (the 32^2 level and the 16^2 bottleneck)
+                const bool deep = r3 == 7 && (Wl == 32 || Wl == 16) && (Hl * Wl) % 64 == 0 && P % 64 == 0;
+                if ((r3 == 4 || r3 == 7) && (Wl % 64 == 0 || deep) && C.cin % 128 == 0 && C.cout % 128 == 0 &&
+                    wc.pps % 64 == 0)
+                    t16 = r3;
+            }
         }
-        WgradArgs w{};
-        w.xcd = xcd_remap_wgrad(c);
-        w.H = Hl;
-        w.W = Wl;
-        w.P = (int)P;
-        w.a = a.ptr;
-        w.lda = a.ld;
-        w.aoff = a.off;
-        w.CA = C.cin;
-        w.amode = G_CONV3;
-        w.ascale = a.scale;
-        w.ashift = a.shift;
-        w.arelu = a.relu;
-        w.b = dout;
-        w.ldb = C.cout;
-        w.boff = 0;
-        w.CB = C.cout;
-        w.bmode = G_IDENT;
-        w.by = p.y[i];
-        w.ldby = p.ldy[i];
-        w.offby = p.offy[i];
-        w.bcoef = dzw ? p.coef : nullptr;
-        w.dzout = dzw ? p.gdz : nullptr;
-        w.bdznomask = dz_mask ? 0 : 1;
-        w.lddz = C.cout;
-        w.bias_slab = C.b >= 0 ? p.bslab : nullptr;
-        w.Mw = 9 * C.cin;
-        w.Nw = C.cout;
-        w.pps = wc.pps;
-        w.splits = wc.splits;
-        w.slab = p.slab;
-        w.bf16 = c->bf16;
-        if (p.x16[i]) {
-            w.a = (const float*)p.x16[i];
-            w.lda = C.cin;
-            w.aoff = 0;
-            w.ascale = w.ashift = nullptr;
-            w.arelu = 0;
-            w.b = (const float*)p.s16;
-            w.by = nullptr;
-            w.bcoef = nullptr;
-            w.zero16 = p.zero16;
-            w.xcd = xcd16_on(c);
-            // (the split count, sized for >= 2048 128x128 tiles, gives >= 512 256x256 ones)
-            int t = wg16_tile(c, C.cin, C.cout);
-            // option wg16_r3: the tap-row kernel (three taps per block from one halo row)
-            const int r3 = c->opt.wg16_r3;
-            // (r06) tile 7 also at W = 32 / 16 (the 32^2 level and the 16^2 bottleneck)
-            const bool deep = r3 == 7 && (Wl == 32 || Wl == 16) && (Hl * Wl) % 64 == 0 && P % 64 == 0;
-            if ((r3 == 4 || r3 == 7) && (Wl % 64 == 0 || deep) && C.cin % 128 == 0 && C.cout % 128 == 0 &&
-                wc.pps % 64 == 0)
-                t = r3;
-            int wbm = 0, wbn = 0, wst = 0;
-            wgrad16g_tile_dims(t, &wbm, &wbn, &wst);
-            char lb[96];
-            snprintf(lb, sizeof lb, "conv_wgrad/wg16%s_%dx%ds%d|%d",
-                     t == 4 ? "r3" : t == 7 ? "r3m" : "", wbm, wbn, wst, i);
-            RUN(lb, 2.0 * P * C.cout * 9 * C.cin, launch_wgrad16(w, t, s));
-        } else {
-            RUN(wlabel("conv_wgrad", wc, i), 2.0 * P * C.cout * 9 * C.cin, launch_wgrad(w, wc.tile, s));
-        }
+        if ((rc = run_wgrad(ps, "conv_wgrad", i, flop, rt.wgrad, wc, w, t16))) return rc;
         RUN("wgrad_reduce", 0,
             k_slab_reduce(p.slab, wc.splits, w.Mw, w.Nw, 0, C.cin, C.cout, grads + C.w, s));
-        if (C.b >= 0) RUN("bias_grad", 0, k_bias_reduce(p.bslab, wc.splits, 1, C.cout, grads + C.b, s));
-        if (dx) {
-            RowGemmArgs g{};
-            g.zero16 = p.zero16;
-            g.H = Hl;
-            g.W = Wl;
-            g.M = (int)P;
-            g.N = C.cin;
-            g.K = 9 * C.cout;
-            g.a = dzw ? p.gdz : dout;
-            g.lda = C.cout;
-            g.aoff = 0;
-            g.C = C.cout;
-            g.amode = G_CONV3;
-            g.ay = p.y[i];
-            g.lday = p.ldy[i];
-            g.offay = p.offy[i];
-            set_weights(c, g, p.pack + C.pd);
-            g.out = dx;
-            g.ldo = ldx;
-            g.ooff = 0;
-            g.emode = accumulate ? E_ADD : E_STORE;
-            if (bn_next) {
-                g.emode = E_STORE_BN;
-                g.ey = p.y[i - 1];
-                g.ldey = p.ldy[i - 1];
-                g.offey = p.offy[i - 1];
-                if (c->bn_relu) {
-                    g.escale = p.scale[i - 1];
-                    g.eshift = p.shift[i - 1];
-                }
-                g.stats = p.part;
-            }
-            if (dz16 && rg16_on(c, C.cout, C.cin)) {
-                use_a16(c, p, g, C.cout);
-                const int tile = rg16_tile(c, g);
-                if (rows) *rows = bn_groups(P);
-                RUN(tlabel16("conv_dgrad", tile, i), 2.0 * P * C.cout * 9 * C.cin,
-                    launch_rowgemm16(g, tile, s));
-                return 0;
-            }
-            if (rows) *rows = bn_groups(P);
-            const int tile = pick_tile(c, C.cin, true, c->bf16);
-            RUN(tlabel("conv_dgrad", tile, i), 2.0 * P * C.cout * 9 * C.cin, launch_rowgemm(g, tile, s));
-        }
-        return 0;
+        if (rt.wgrad != FAM_X3 && C.b >= 0)
+            RUN("bias_grad", 0, k_bias_reduce(p.bslab, wc.splits, 1, C.cout, grads + C.b, s));
+        if (!dx) return 0;
+        // the input gradient: A = dz (f32: in place in dout, or the copy the weight gradient
+        // stored; LDS-DMA / x3: its scratch image)
+        RowGemmArgs g = rowgemm_at(p, C.level, C.cin, 9 * C.cout);
+        g.a = dzw ? p.gdz : dout;
+        g.lda = C.cout;
+        g.C = C.cout;
+        g.amode = G_CONV3;
+        g.ay = p.y[i];
+        g.lday = p.ldy[i];
+        g.offay = p.offy[i];
+        g.a16 = scratch_image(p, rt.dgrad);
+        g.out = dx;
+        g.ldo = ldx;
+        g.emode = accumulate ? E_ADD : E_STORE;
+        if (bn_next) bn_epilogue(c, p, g, i - 1);
+        if (rows) *rows = bn_groups(P);
+        return run_rowgemm(ps, "conv_dgrad", i, flop, rt.dgrad, true, p.pack + C.pd, g);
     };
     // ConvT k backward: dOut = up half of dcat[lo]; dx = `do` of its input's BN (partials ->
     // rows)
     auto convT_bwd = [&](int k, float* dx, int* rows) -> int {
         const ConvTL& T = c->convt[k];
+        const Route& rt = p.rt.convt[k];
         const int src = 2 * (D + k) + 1;
         const int lo = T.in_level - 1;
-        const int ldo = 2 * c->ch(lo), uo = c->up_off(lo);
         const int Hi = H >> T.in_level, Wi = W >> T.in_level;
         const int64_t Pin = p.P[T.in_level];
-        if (p.pack3 && x3_convt_on(c, T.cin, T.cout)) {
-            // option x3: the up half of the concat gradient as an x3 image feeds the weight
-            // gradient (B', gathered 2x2) and the input gradient (A)
-            RUN("prep_x3", 0, k_to_x3(p.dcat[lo], ldo, uo, T.cout, nullptr, nullptr, 0, p.P[lo], p.s3,
-                                      T.cout, 0, s));
-            const WgradCfg wc = x3_wgrad_cfg(c, T.cin, 1, T.cout, 4, Pin);
-            WgradArgs w{};
-            w.xcd = 1;
-            w.H = Hi;
-            w.W = Wi;
-            w.P = (int)Pin;
-            w.a = (const float*)p.t3[k];
-            w.lda = T.cin;
-            w.CA = T.cin;
-            w.amode = G_IDENT;
-            w.b = (const float*)p.s3;
-            w.ldb = T.cout;
-            w.CB = T.cout;
-            w.bmode = G_UP2;
-            w.Mw = T.cin;
-            w.Nw = 4 * T.cout;
-            w.pps = wc.pps;
-            w.splits = wc.splits;
-            w.slab = p.slab;
-            w.zero16 = p.zero16;
-            RUN(x3wlabel("convT_wgrad", wc, 100 + k), 2.0 * Pin * T.cin * 4 * T.cout,
-                launch_wgrad_x3(w, wc.tile, s));
-            RUN("bias_grad", 0, k_up2_bias_partials(p.dcat[lo], ldo, uo, Hi, Wi, Pin, T.cout, wc.pps,
-                                                    wc.splits, p.bslab, s));
-            RUN("wgrad_reduce", 0,
-                k_slab_reduce(p.slab, wc.splits, w.Mw, w.Nw, 1, T.cin, T.cout, grads + T.w, s));
-            RUN("bias_grad", 0, k_bias_reduce(p.bslab, wc.splits, 4, T.cout, grads + T.b, s));
-            RowGemmArgs g{};
-            g.H = Hi;
-            g.W = Wi;
-            g.M = (int)Pin;
-            g.N = T.cin;
-            g.K = 4 * T.cout;
-            g.C = T.cout;
-            g.amode = G_UP2;
-            use_x3(c, p, g, p.s3, T.cout, p.pack3 + 3 * T.pd);
-            g.out = dx;
-            g.ldo = T.cin;
-            g.ooff = 0;
-            if (c->res) {  // d(block output); the block's own backward entry masks it
-                g.emode = E_STORE;
-            } else {
-                g.emode = E_STORE_BN;
-                g.ey = p.y[src];
-                g.ldey = p.ldy[src];
-                g.offey = p.offy[src];
-                if (c->bn_relu) {
-                    g.escale = p.scale[src];
-                    g.eshift = p.shift[src];
-                }
-                g.stats = p.part;
-            }
-            const int tile = x3_tile(c, g);
-            *rows = bn_groups(Pin);
-            RUN(xlabel("convT_dgrad", tile, 100 + k), 2.0 * Pin * T.cin * 4 * T.cout,
-                launch_rowgemm_x3(g, tile, s));
-            return 0;
-        }
-        WgradCfg wc = wgrad_cfg(c, T.cin, 1, T.cout, 4, Pin, c->bf16);
-        WgradArgs w{};
+        const double flop = 2.0 * Pin * T.cin * 4 * T.cout;
+        const Operand up{p.dcat[lo], 2 * c->ch(lo), c->up_off(lo), nullptr, nullptr, 0};
+        // the up half of the concat gradient as a bf16 / x3 image in the scratch image: B'
+        // (gathered 2x2) of an image weight gradient, A of an image input gradient
+        const bool wimg = rt.wgrad != FAM_REG;
+        if (wimg && (rc = prep_image(L, rt.wgrad, up, 0, T.cout, p.P[lo], scratch_image(p, rt.wgrad), T.cout)))
+            return rc;
+        const WgradCfg wc = convt_wgrad_cfg(c, p, k);
+        WgradArgs w = wgrad_at(c, p, T.in_level, wc);
         w.xcd = xcd_remap_wgrad(c);
-        w.H = Hi;
-        w.W = Wi;
-        w.P = (int)Pin;
-        if (c->res) {
-            w.a = p.out[D + k];
-            w.lda = p.ldout[D + k];
-            w.aoff = p.offout[D + k];
-        } else {
-            w.a = p.y[src];
-            w.lda = p.ldy[src];
-            w.aoff = p.offy[src];
-            w.ascale = p.scale[src];
-            w.ashift = p.shift[src];
-            w.arelu = c->bn_relu ? T.cin : 0;
-        }
+        set_operand(w, convt_input(c, p, k));
         w.CA = T.cin;
         w.amode = G_IDENT;
-        w.b = p.dcat[lo];
-        w.ldb = ldo;
-        w.boff = uo;
+        w.b = up.ptr;
+        w.ldb = up.ld;
+        w.boff = up.off;
         w.CB = T.cout;
         w.bmode = G_UP2;
         w.bias_slab = p.bslab;
         w.Mw = T.cin;
         w.Nw = 4 * T.cout;
-        w.pps = wc.pps;
-        w.splits = wc.splits;
-        w.slab = p.slab;
-        w.bf16 = c->bf16;
-        const bool t16 = p.t16[k] != nullptr;
-        if (t16) {
-            // bf16 image of the up half of the concat gradient: B' here, A of the dgrad below
-            RUN("prep16", 0, k_to_bf16(p.dcat[lo], ldo, uo, T.cout, nullptr, nullptr, 0, p.P[lo],
-                                       p.s16, s));
-            w.a = (const float*)p.t16[k];
-            w.lda = T.cin;
-            w.aoff = 0;
-            w.ascale = w.ashift = nullptr;
-            w.arelu = 0;
-            w.b = (const float*)p.s16;
-            w.ldb = T.cout;
-            w.boff = 0;
+        if (wimg) {  // from the forward's kept image; the bias gradient from its own pass
+            use_images(c, p, w, rt.wgrad, rt.wgrad == FAM_X3 ? p.t3[k] : p.t16[k]);
             w.bias_slab = nullptr;
-            w.zero16 = p.zero16;
-            w.xcd = xcd16_on(c);
-            const int t = wg16_tile(c, T.cin, T.cout);
-            int wbm = 0, wbn = 0, wst = 0;
-            wgrad16g_tile_dims(t, &wbm, &wbn, &wst);
-            char lb[96];
-            snprintf(lb, sizeof lb, "convT_wgrad/wg16_%dx%ds%d|%d", wbm, wbn, wst, 100 + k);
-            RUN(lb, 2.0 * Pin * T.cin * 4 * T.cout, launch_wgrad16(w, t, s));
-            RUN("bias_grad", 0, k_up2_bias_partials(p.dcat[lo], ldo, uo, Hi, Wi, Pin, T.cout, wc.pps,
-                                                    wc.splits, p.bslab, s));
-        } else {
-            RUN(wlabel("convT_wgrad", wc, 100 + k), 2.0 * Pin * T.cin * 4 * T.cout,
-                launch_wgrad(w, wc.tile, s));
         }
+        if ((rc = run_wgrad(ps, "convT_wgrad", 100 + k, flop, rt.wgrad, wc, w))) return rc;
+        if (wimg)
+            RUN("bias_grad", 0, k_up2_bias_partials(up.ptr, up.ld, up.off, Hi, Wi, Pin, T.cout, wc.pps,
+                                                    wc.splits, p.bslab, s));
         RUN("wgrad_reduce", 0,
             k_slab_reduce(p.slab, wc.splits, w.Mw, w.Nw, 1, T.cin, T.cout, grads + T.w, s));
         RUN("bias_grad", 0, k_bias_reduce(p.bslab, wc.splits, 4, T.cout, grads + T.b, s));
-        RowGemmArgs g{};
-        g.zero16 = p.zero16;
-        g.H = Hi;
-        g.W = Wi;
-        g.M = (int)Pin;
-        g.N = T.cin;
-        g.K = 4 * T.cout;
-        g.a = p.dcat[lo];
-        g.lda = ldo;
-        g.aoff = uo;
+        if (!wimg && rt.dgrad != FAM_REG &&
+            (rc = prep_image(L, rt.dgrad, up, 0, T.cout, p.P[lo], scratch_image(p, rt.dgrad), T.cout)))
+            return rc;
+        RowGemmArgs g = rowgemm_at(p, T.in_level, T.cin, 4 * T.cout);
+        set_operand(g, up);
         g.C = T.cout;
         g.amode = G_UP2;
-        set_weights(c, g, p.pack + T.pd);
+        g.a16 = scratch_image(p, rt.dgrad);
         g.out = dx;
         g.ldo = T.cin;
-        g.ooff = 0;
-        if (c->res) {  // d(block output); the block's own backward entry masks it
+        if (c->res)  // d(block output); the block's own backward entry masks it
             g.emode = E_STORE;
-        } else {
-            g.emode = E_STORE_BN;
-            g.ey = p.y[src];
-            g.ldey = p.ldy[src];
-            g.offey = p.offy[src];
-            if (c->bn_relu) {
-                g.escale = p.scale[src];
-                g.eshift = p.shift[src];
-            }
-            g.stats = p.part;
-        }
-        if (rg16_on(c, T.cout, T.cin)) {
-            if (!t16) {
-                RUN("prep16", 0, k_to_bf16(p.dcat[lo], ldo, uo, T.cout, nullptr, nullptr, 0, p.P[lo],
-                                           p.s16, s));
-            }
-            use_a16(c, p, g, T.cout);
-            const int tile = rg16_tile(c, g);
-            *rows = bn_groups(Pin);
-            RUN(tlabel16("convT_dgrad", tile, 100 + k), 2.0 * Pin * T.cin * 4 * T.cout,
-                launch_rowgemm16(g, tile, s));
-            return 0;
-        }
-        const int tile = pick_tile(c, T.cin, true, c->bf16, true);
+        else
+            bn_epilogue(c, p, g, src);
         *rows = bn_groups(Pin);
-        RUN(tlabel("convT_dgrad", tile, 100 + k), 2.0 * Pin * T.cin * 4 * T.cout, launch_rowgemm(g, tile, s));
-        return 0;
+        return run_rowgemm(ps, "convT_dgrad", 100 + k, flop, rt.dgrad, true, p.pack + T.pd, g);
     };
     // gradient bucket b is final once stage bucket_stage[b] is done: record its event (a
     // channel-padded network first compacts the bucket's tensors into the caller's arena,
@@ -1883,30 +1808,24 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         // input gradient is ADDED to the skip's in dx (ld ldx; null for the first block).
         auto block_bwd = [&](int b, float* dx, int ldx) -> int {
             const ConvL& CL = c->conv[2 * b];
+            const Route& rt = p.rt.skip[b];
             const int i1 = 2 * b, i2 = 2 * b + 1;
             const int64_t P = p.P[CL.level];
+            const double flop = 2.0 * P * CL.cin * CL.cout;
             // bf16 math: du's bf16 image with it, where an LDS-DMA skip GEMM reads it (the scratch
             // image is free until conv2's dz pass, which follows the skip's GEMMs)
-            const bool sk_wg16 = CL.pf >= 0 && p.x16[i1] != nullptr;
-            const bool sk_rg16 = CL.pf >= 0 && dx && rg16_on(c, CL.cout, CL.cin);
+            const bool du16 = rt.wgrad == FAM_DMA16 || rt.dgrad == FAM_DMA16;
             RUN("res_bwd_prep", 0, k_res_bwd_prep(G0, p.out[b], p.ldout[b], p.offout[b], p.y[i2], P,
-                                                  CL.cout, p.part, RED_G, s,
-                                                  sk_wg16 || sk_rg16 ? p.s16 : nullptr));
-            if (CL.pf < 0) {
+                                                  CL.cout, p.part, RED_G, s, du16 ? p.s16 : nullptr));
+            if (rt.wgrad == FAM_NONE) {
                 RUN("skip_wgrad", 2.0 * P * CL.cout,
                     k_res_first_wgrad(p.x_nhwc, G0, (int)P, CL.cout, p.hpart, RED_G,
                                       grads + c->skip_w[b], s));
             } else {
-                Operand a = conv_input(c, p, i1);
-                WgradCfg wc = wgrad_cfg(c, CL.cin, 1, CL.cout, 1, P, c->bf16);
-                WgradArgs w{};
+                const WgradCfg wc = wgrad_cfg(c, CL.cin, 1, CL.cout, 1, P, c->bf16);
+                WgradArgs w = wgrad_at(c, p, CL.level, wc);
                 w.xcd = xcd_remap_wgrad(c);
-                w.H = H >> CL.level;
-                w.W = W >> CL.level;
-                w.P = (int)P;
-                w.a = a.ptr;
-                w.lda = a.ld;
-                w.aoff = a.off;
+                set_operand(w, conv_input(c, p, i1));
                 w.CA = CL.cin;
                 w.amode = G_IDENT;
                 w.b = G0;
@@ -1915,52 +1834,22 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
                 w.bmode = G_IDENT;
                 w.Mw = CL.cin;
                 w.Nw = CL.cout;
-                w.pps = wc.pps;
-                w.splits = wc.splits;
-                w.slab = p.slab;
-                w.bf16 = c->bf16;
-                if (sk_wg16) {  // A' = the forward's image of the block input, B' = du's image
-                    w.a = (const float*)p.x16[i1];
-                    w.lda = CL.cin;
-                    w.aoff = 0;
-                    w.b = (const float*)p.s16;
-                    w.zero16 = p.zero16;
-                    w.xcd = xcd16_on(c);
-                    const int t = wg16_tile(c, CL.cin, CL.cout);
-                    int wbm = 0, wbn = 0, wst = 0;
-                    wgrad16g_tile_dims(t, &wbm, &wbn, &wst);
-                    char lb[96];
-                    snprintf(lb, sizeof lb, "skip_wgrad/wg16_%dx%ds%d|%d", wbm, wbn, wst, b);
-                    RUN(lb, 2.0 * P * CL.cin * CL.cout, launch_wgrad16(w, t, s));
-                } else
-                RUN(wlabel("skip_wgrad", wc, b), 2.0 * P * CL.cin * CL.cout, launch_wgrad(w, wc.tile, s));
+                // A' = the forward's image of the block input (conv1 keeps it), B' = du's image
+                if (rt.wgrad == FAM_DMA16) use_images(c, p, w, FAM_DMA16, p.x16[i1]);
+                if ((rc = run_wgrad(ps, "skip_wgrad", b, flop, rt.wgrad, wc, w))) return rc;
                 RUN("wgrad_reduce", 0, k_slab_reduce(p.slab, wc.splits, w.Mw, w.Nw, 2, CL.cin, CL.cout,
                                                      grads + c->skip_w[b], s));
-                RowGemmArgs g{};
-                g.zero16 = p.zero16;
-                g.H = H >> CL.level;
-                g.W = W >> CL.level;
-                g.M = (int)P;
-                g.N = CL.cin;
-                g.K = CL.cout;
+                RowGemmArgs g = rowgemm_at(p, CL.level, CL.cin, CL.cout);
                 g.a = G0;
                 g.lda = CL.cout;
                 g.C = CL.cout;
                 g.amode = G_IDENT;
-                set_weights(c, g, p.pack + c->skip_pd[b]);
+                g.a16 = p.s16;
                 g.out = dx;
                 g.ldo = ldx;
                 g.emode = E_STORE;
-                if (sk_rg16) {
-                    use_a16(c, p, g, CL.cout);
-                    const int tile = rg16_tile(c, g);
-                    RUN(tlabel16("skip_dgrad", tile, b), 2.0 * P * CL.cin * CL.cout,
-                        launch_rowgemm16(g, tile, s));
-                } else {
-                    const int tile = pick_tile(c, CL.cin, true, c->bf16);
-                    RUN(tlabel("skip_dgrad", tile, b), 2.0 * P * CL.cin * CL.cout,
-                        launch_rowgemm(g, tile, s));
-                }
+                if ((rc = run_rowgemm(ps, "skip_dgrad", b, flop, rt.dgrad, true, p.pack + c->skip_pd[b], g)))
+                    return rc;
             }
             if ((rc = bn_finalize(i2, RED_G))) return rc;
             if ((rc = conv_bwd(i2, G0, G1, CL.cout, true, &R))) return rc;
@@ -2001,11 +1890,7 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
     // (r05) one output channel on the x3 path (r06: and on the bf16 path's LDS-DMA GEMMs): the
     // last conv's dz pass recomputes `do` = mask * dl * w from the logit gradient, so head_bwd
     // stores no full-resolution f32 `do`
-    const ConvL& CL = c->conv[last];
-    const bool head_fuse = c->out_ch == 1 && CL.cout == c->base && c->opt.head_fuse &&
-                           ((p.pack3 && x3_conv_on(c, CL.cin, CL.cout)) ||
-                            (c->bf16 && p.x16[last] && rg16_on(c, CL.cout, CL.cin)));
-    head_src_conv = head_fuse ? last : -1;
+    const bool head_fuse = p.rt.conv[last].head_fuse;
     RUN("head_bwd", 2.0 * p.P[0] * c->base * c->out_ch * 2,
         k_head_bwd(p.y[last], c->base, p.scale[last], p.shift[last], c->bn_relu ? 1 : 0,
                    prm + c->head_w, c->out_ch, (int)p.P[0], H * W, dlogits, head_fuse ? nullptr : G0,
@@ -2043,16 +1928,9 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         // up to 2048 blocks on the large levels (512 left the pass at ~4.7 TB/s); the partial
         // rows fit: p.part holds P/64 + 1 rows of 2C for every conv of the level
         const int Gmp = wide_g(p.P[b]);
-        const ConvL& C1 = c->conv[i1];
-        // x3: the conv's x3 dz pass; bf16 (r06): its bf16 dz pass, where no f32 dz is needed
-        // (the LDS-DMA dgrad and weight gradient read the bf16 image only)
-        const bool pool_fuse =
-            c->opt.pool_fuse && !c->res && C1.cout == C && p.P[b] < (1 << 24) &&
-            ((p.pack3 && x3_conv_on(c, C1.cin, C1.cout)) ||
-             (c->bf16 && p.x16[i1] && rg16_on(c, C1.cout, C1.cin)));
+        const bool pool_fuse = p.rt.conv[i1].pool_fuse;
         pool_src = PoolSrc{};
         if (pool_fuse) {
-            pool_src.conv = i1;
             pool_src.dp = cur;
             pool_src.idx = p.idx[b];
             pool_src.dskip = p.dcat[b] + c->skip_off(b);
@@ -2558,12 +2436,11 @@ int unet_debug_view(unet_ctx* c, int N, int H, int W, int training, int kind, in
         if (kind == 5) {
             // the x3 path's max-pool writes the next conv's x3 image instead (forward_impl):
             // the f32 pooled buffer is never written there
-            const ConvL& Cj = c->conv[2 * (index + 1)];
-            if (!c->res && p.pack3 && x3_conv_on(c, Cj.cin, Cj.cout))
-                return fail(c, UNET_ERR_INVALID, "debug view 5: level %d pools into an x3 image", index);
             // (r06) ... and a bf16 training pass pools into the next conv's bf16 image
-            if (!c->res && training && c->bf16 && wg16_on(c, Cj.cin, Cj.cout) && rg16_on(c, Cj.cin, Cj.cout))
-                return fail(c, UNET_ERR_INVALID, "debug view 5: level %d pools into a bf16 image", index);
+            const Route& rj = p.rt.conv[2 * (index + 1)];
+            if (rj.up == W_POOL)
+                return fail(c, UNET_ERR_INVALID, "debug view 5: level %d pools into %s image", index,
+                            rj.fwd == FAM_X3 ? "an x3" : "a bf16");
             q = p.pool[index];
             n = p.P[index + 1] * C;
             l = C;

@@ -1,6 +1,6 @@
 // Exact three-way bf16 split of an f32 value, v = h + m + l (kernels_gemm_x3.hip header), with
 // the range edges made explicit.  One source for the device passes (to_x3, bn_dz_x3, the ConvT
-// epilogue into an x3 image) and the host test hook unet_x3_split_host (runtime.hip), which
+// epilogue into an x3 image) and the host test hook unet_x3_split_host (ops_abi.hip), which
 // tests/test_lib_cpu.py checks against the NumPy restatement in tests/x3_split_ref.py; the GPU
 // test tests/test_gpu_x3.py checks the device bits against the same restatement.
 //
