@@ -549,7 +549,10 @@ int unet_timing_read(unet_ctx* ctx, int i, const char** family, int64_t* launche
  *       the max-pool then stores that conv's x3 operand image instead), 6 concat buffer[l]
  *       (NHWC, 2*64<<l channels),
  *       7 d(concat)[l] of the last backward, 8 max-pool winner index[l] (uint8 NHWC dense,
- *       window position 0..3 in torch's scan order).  *count = elements (pixels*ld for NHWC). */
+ *       window position 0..3 in torch's scan order), 9 (ResUNet only) out[b], the stored output
+ *       ReLU(BN2(z2) + skip(x)) of residual block b = 0 .. 2 depth (encoders, bottleneck,
+ *       decoders; NHWC, channel stride *ld, channel offset *off: an encoder's lives in the skip
+ *       half of its concat buffer).  *count = elements (pixels*ld for NHWC). */
 int unet_debug_view(unet_ctx* ctx, int N, int H, int W, int training, int kind, int index,
                     int64_t* byte_offset, int64_t* count, int* ld, int* off);
 

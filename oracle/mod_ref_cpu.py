@@ -130,23 +130,76 @@ def _convT(x, w, b, bf16):
         b.view(1, -1, 1, 1)
 
 
+# test hooks, with the meaning they have in unet_ref_cpu.forward: boolean NCHW masks that replace
+# the ReLU decisions in forward order (ReLU(z) becomes z * mask) and max-pool winner indices (N,
+# C, Ho, Wo; window position 0..3 in torch's scan order) that replace the pools' (a gather), so
+# an evaluation in one precision can follow the branches another evaluation took.  _RECORD: a
+# pair of lists that receives the decisions (z > 0, first maximum of the window) an evaluation
+# takes itself.  All three are None outside a forward that was given them.
+_RELU_MASKS = None
+_POOL_IDX = None
+_RECORD = None
+
+
+def _windows(x):
+    N, C, H, W = x.shape
+    return x.reshape(N, C, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(N, C, H // 2, W // 2, 4)
+
+
+def _relu(x):
+    if _RECORD is not None:
+        _RECORD[0].append((x > 0).detach() if _RELU_MASKS is None else _RELU_MASKS[0])
+    if _RELU_MASKS is None:
+        return F.relu(x)
+    return x * _RELU_MASKS.pop(0).to(x.dtype)
+
+
+def _maxpool(x):
+    if _RECORD is not None:
+        _RECORD[1].append(_windows(x.detach()).max(-1).indices.to(torch.uint8)
+                          if _POOL_IDX is None else _POOL_IDX[0])
+    if _POOL_IDX is None:
+        return F.max_pool2d(x, 2, 2)
+    return _windows(x).gather(-1, _POOL_IDX.pop(0).long().unsqueeze(-1)).squeeze(-1)
+
+
+def run_with_branches(fn, relu_masks=None, pool_idx=None, record=None):
+    """fn() with the hooks above set; every mask and index given must have been consumed."""
+    global _RELU_MASKS, _POOL_IDX, _RECORD
+    _RELU_MASKS = None if relu_masks is None else list(relu_masks)
+    _POOL_IDX = None if pool_idx is None else list(pool_idx)
+    _RECORD = record
+    try:
+        out = fn()
+        assert not _RELU_MASKS and not _POOL_IDX, "more branch decisions given than the network takes"
+        return out
+    finally:
+        _RELU_MASKS = _POOL_IDX = _RECORD = None
+
+
 def _block(x, P, B, prefix, training, bf16=False, first=False):
     # mod.py:43-51 (the Cin = 1 first conv runs in f32 on the HIP path too)
     x = _conv3(x, P[f"{prefix}.0.weight"], bf16 and not first)
-    x = F.relu(O._bn(x, P, B, f"{prefix}.1", training))
+    x = _relu(O._bn(x, P, B, f"{prefix}.1", training))
     x = _conv3(x, P[f"{prefix}.3.weight"], bf16)
-    return F.relu(O._bn(x, P, B, f"{prefix}.4", training))
+    return _relu(O._bn(x, P, B, f"{prefix}.4", training))
 
 
 def make_forward(depth, bf16=False):
-    """forward(x, P, B, training) of mod.py:UNet with `depth` levels (mod.py:53-66)."""
+    """forward(x, P, B, training) of mod.py:UNet with `depth` levels (mod.py:53-66).
+    relu_masks / pool_idx: optional 2 (2 depth + 1) boolean NCHW masks (one after each BN, forward
+    order) / `depth` winner-index tensors that replace the ReLUs' / max-pools' decisions;
+    record: optional pair of lists that receives the decisions taken (test hooks)."""
 
-    def forward(x, P, B, training=True):
+    def forward(x, P, B, training=True, relu_masks=None, pool_idx=None, record=None):
+        return run_with_branches(lambda: _forward(x, P, B, training), relu_masks, pool_idx, record)
+
+    def _forward(x, P, B, training):
         skips = []
         for i in range(depth):
             x = _block(x, P, B, f"encoders.{i}", training, bf16, first=(i == 0))
             skips.append(x)
-            x = F.max_pool2d(x, 2, 2)
+            x = _maxpool(x)
         x = _block(x, P, B, "bottleneck", training, bf16)
         for j, skip in enumerate(reversed(skips)):
             x = _convT(x, P[f"upconvs.{j}.weight"], P[f"upconvs.{j}.bias"], bf16)
@@ -159,10 +212,20 @@ def make_forward(depth, bf16=False):
     return forward
 
 
-def train_step(P, B, opt, x, t, depth, w_bce=1.0, w_dice=1.0, shards=1, bf16=False):
-    """utils/trainer.py:81-93 with mod.py:UNet as the model."""
+def _pinned(fwd, relu_masks, pool_idx, record):
+    if relu_masks is None and pool_idx is None and record is None:
+        return fwd
+    return lambda x, P, B, training: fwd(x, P, B, training, relu_masks=relu_masks,
+                                         pool_idx=pool_idx, record=record)
+
+
+def train_step(P, B, opt, x, t, depth, w_bce=1.0, w_dice=1.0, shards=1, bf16=False,
+               relu_masks=None, pool_idx=None, record=None):
+    """utils/trainer.py:81-93 with mod.py:UNet as the model (relu_masks / pool_idx / record: the
+    hooks of make_forward, one shard only)."""
+    assert shards == 1 or (relu_masks is None and pool_idx is None and record is None)
     return O.train_step(P, B, opt, x, t, w_bce, w_dice, shards,
-                        forward_fn=make_forward(depth, bf16))
+                        forward_fn=_pinned(make_forward(depth, bf16), relu_masks, pool_idx, record))
 
 
 # ---------------------------------------------------------------- ResUNet (mod.py:71-131)
@@ -225,21 +288,26 @@ def res_make_params(seed=42, base=64, depth=5, gamma_lo=0.5, gamma_hi=1.5, in_ch
 def _res_block(x, P, B, prefix, training):
     # mod.py:85-86: relu(conv(x) + skip(x)), conv = Conv-BN-ReLU-Conv-BN (mod.py:75-81)
     y = F.conv2d(x, P[f"{prefix}.conv.0.weight"], None, padding=1)
-    y = F.relu(O._bn(y, P, B, f"{prefix}.conv.1", training))
+    y = _relu(O._bn(y, P, B, f"{prefix}.conv.1", training))
     y = F.conv2d(y, P[f"{prefix}.conv.3.weight"], None, padding=1)
     y = O._bn(y, P, B, f"{prefix}.conv.4", training)
-    return F.relu(y + F.conv2d(x, P[f"{prefix}.skip.weight"]))
+    return _relu(y + F.conv2d(x, P[f"{prefix}.skip.weight"]))
 
 
 def make_res_forward(depth):
-    """forward(x, P, B, training) of mod.py:ResUNet (mod.py:112-124)."""
+    """forward(x, P, B, training) of mod.py:ResUNet (mod.py:112-124).  relu_masks / pool_idx /
+    record as in make_forward: two decisions per block, the inner ReLU after BN1 and the outer
+    ReLU of conv(x) + skip(x), and `depth` pools."""
 
-    def forward(x, P, B, training=True):
+    def forward(x, P, B, training=True, relu_masks=None, pool_idx=None, record=None):
+        return run_with_branches(lambda: _forward(x, P, B, training), relu_masks, pool_idx, record)
+
+    def _forward(x, P, B, training):
         skips = []
         for i in range(depth):
             x = _res_block(x, P, B, f"encoders.{i}", training)
             skips.append(x)
-            x = F.max_pool2d(x, 2, 2)
+            x = _maxpool(x)
         x = _res_block(x, P, B, "bottleneck", training)
         for j, skip in enumerate(reversed(skips)):
             x = F.conv_transpose2d(x, P[f"upconvs.{j}.weight"], P[f"upconvs.{j}.bias"], stride=2)
@@ -252,9 +320,12 @@ def make_res_forward(depth):
     return forward
 
 
-def res_train_step(P, B, opt, x, t, depth, w_bce=1.0, w_dice=1.0, shards=1):
+def res_train_step(P, B, opt, x, t, depth, w_bce=1.0, w_dice=1.0, shards=1, relu_masks=None,
+                   pool_idx=None, record=None):
     """utils/trainer.py:81-93 with mod.py:ResUNet (the model main.py:122 builds)."""
-    return O.train_step(P, B, opt, x, t, w_bce, w_dice, shards, forward_fn=make_res_forward(depth))
+    assert shards == 1 or (relu_masks is None and pool_idx is None and record is None)
+    return O.train_step(P, B, opt, x, t, w_bce, w_dice, shards,
+                        forward_fn=_pinned(make_res_forward(depth), relu_masks, pool_idx, record))
 
 
 def conv_macs_per_image(H, W, in_channels=1, out_channels=1, base=64, depth=5):

@@ -24,21 +24,25 @@ def _skip(x, w, bf16):
 
 def _res_block(x, P, B, prefix, training, bf16=False, first=False):
     y = MO._conv3(x, P[f"{prefix}.conv.0.weight"], bf16 and not first)
-    y = F.relu(O._bn(y, P, B, f"{prefix}.conv.1", training))
+    y = MO._relu(O._bn(y, P, B, f"{prefix}.conv.1", training))
     y = MO._conv3(y, P[f"{prefix}.conv.3.weight"], bf16)
     y = O._bn(y, P, B, f"{prefix}.conv.4", training)
-    return F.relu(y + _skip(x, P[f"{prefix}.skip.weight"], bf16 and not first))
+    return MO._relu(y + _skip(x, P[f"{prefix}.skip.weight"], bf16 and not first))
 
 
 def make_res_forward(depth, bf16=False):
-    """forward(x, P, B, training) of mod.py:ResUNet with `depth` levels."""
+    """forward(x, P, B, training) of mod.py:ResUNet with `depth` levels; relu_masks / pool_idx /
+    record are the branch hooks of mod_ref_cpu.make_res_forward."""
 
-    def forward(x, P, B, training=True):
+    def forward(x, P, B, training=True, relu_masks=None, pool_idx=None, record=None):
+        return MO.run_with_branches(lambda: _forward(x, P, B, training), relu_masks, pool_idx, record)
+
+    def _forward(x, P, B, training):
         skips = []
         for i in range(depth):
             x = _res_block(x, P, B, f"encoders.{i}", training, bf16, first=(i == 0))
             skips.append(x)
-            x = F.max_pool2d(x, 2, 2)
+            x = MO._maxpool(x)
         x = _res_block(x, P, B, "bottleneck", training, bf16)
         for j, skip in enumerate(reversed(skips)):
             x = MO._convT(x, P[f"upconvs.{j}.weight"], P[f"upconvs.{j}.bias"], bf16)
@@ -49,10 +53,11 @@ def make_res_forward(depth, bf16=False):
     return forward
 
 
-def res_train_step(P, B, opt, x, t, depth, bf16=False):
+def res_train_step(P, B, opt, x, t, depth, bf16=False, relu_masks=None, pool_idx=None, record=None):
     """One trainer step (loss = BCE + Dice) of the residual network; P's dtype is the
     evaluation dtype.  B is updated in place (running statistics)."""
-    return O.train_step(P, B, opt, x, t, forward_fn=make_res_forward(depth, bf16))
+    return O.train_step(P, B, opt, x, t, forward_fn=MO._pinned(make_res_forward(depth, bf16),
+                                                               relu_masks, pool_idx, record))
 
 
 def to64(d):

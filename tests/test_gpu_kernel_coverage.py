@@ -2,10 +2,12 @@
 is checked against the fp64 oracle (tests/kernel_cases.py: PRODUCTION, SMALL, key).
 
 test_small_case_vs_fp64 runs one training step per small case with per-launch timing on and
-judges it against the fp64 oracle by the project's existing methods and bars (the masked-fp64
+judges it against the fp64 oracle by the project's methods and bars (the masked-fp64
 step of tests/test_gpu_x3.py for models/model.py UNet; the fp32-oracle envelope of
 test_mod_narrow_full_grads_vs_fp64 / test_res_full_grads_vs_oracle for the f32 mod.py networks;
-the bf16-operand oracle and envelope of test_mod_bf16_matches_bf16_oracle for bf16).  Only a
+the bf16-operand oracle and envelope of test_mod_bf16_matches_bf16_oracle for bf16; for every
+mod.py case also the branch-pinned fp64 check of tests/masked.py, whose bars are ~100x / ~10x
+below those envelopes).  Only a
 case that passed lends its launch keys to the coverage; agreement between two tiles counts for
 nothing here.
 
@@ -24,6 +26,7 @@ import pytest
 import torch
 
 import kernel_cases as KC
+import masked as MK
 import test_gpu_x3 as TX
 from _helpers import grad_errors, hip_mod_model, hip_model, inputs, norm_rel, options, rel_max
 from oracle import mod_ref_cpu as MO
@@ -127,8 +130,11 @@ def _check_unet(c, m, P, x, t, step):
 def _check_f32(c, m, P, x, t, step):
     """test_mod_narrow_full_grads_vs_fp64 / test_res_full_grads_vs_oracle: logits within 1e-4
     of max|ref| of the fp32 oracle; every gradient against the fp64 oracle within 2x the fp32
-    oracle's own worst deviation over x and x (1 + 1e-7), floor 1e-2."""
+    oracle's own worst deviation over x and x (1 + 1e-7), floor 1e-2.  Then the pinned check of
+    tests/masked.py: the same step against the fp64 oracle on this path's own ReLU / max-pool
+    branches, at 4x the pinned fp32 CPU oracle's own error (12x under x3 = 0)."""
     _, bufs, ts = _oracle_fns(c)
+    br = MK.device_branches(m, x, c)
     ref = ts(P, bufs(), x, t)
     refp = ts(P, bufs(), x * (1 + 1e-7), t)
     r64 = ts(_to64(P), _to64(bufs()), x.double(), t.double())
@@ -143,6 +149,8 @@ def _check_f32(c, m, P, x, t, step):
           f"{e32[worst]:.2e}, envelope {env:.2e})")
     assert e_l <= LOGIT_TOL, (c["id"], e_l)
     assert errs[worst] <= env, f"{c['id']} {worst}: {errs[worst]:.3e} (fp32 oracle {e32[worst]:.3e})"
+    MK.check_on_branches(c, P, x, t, br, logits.double(), MK.grads_of(m), c["id"],
+                         c["opts"].get("x3", 1))
     return labels
 
 
@@ -150,8 +158,11 @@ def _check_bf16(c, m, P, x, t, step):
     """test_mod_bf16_matches_bf16_oracle: against the oracle that rounds the operands the HIP
     bf16 kernels round -- logits 2x the oracle's own fp32-vs-fp64 spread + 1e-4, loss 1e-3,
     every gradient 2x the largest spread; distance to the fp32 oracle 5e-2, or twice the bf16
-    oracle's own where that exceeds it (tests/test_gpu_res_bf16.py _fp32_bar)."""
+    oracle's own where that exceeds it (tests/test_gpu_res_bf16.py _fp32_bar).  Then the pinned
+    check of tests/masked.py: against the bf16-operand oracle in fp64 on this path's own
+    branches, at 2x that oracle's pinned fp32-vs-fp64 spread (at most 5e-2)."""
     _, bufs, ts = _oracle_fns(c)
+    br = MK.device_branches(m, x, c)
     ref = ts(P, bufs(), x, t, bf16=True)
     r64 = ts(_to64(P), _to64(bufs()), x.double(), t.double(), bf16=True)
     ref32 = ts(P, bufs(), x, t)
@@ -172,6 +183,7 @@ def _check_bf16(c, m, P, x, t, step):
     assert abs(loss - ref["loss"].item()) <= 1e-3
     assert errs[worst] <= env, f"{c['id']} {worst}: {errs[worst]:.3e} (envelope {env:.3e})"
     assert e_l32 <= bar32, (c["id"], e_l32, bar32)
+    MK.check_on_branches(c, P, x, t, br, logits.double(), MK.grads_of(m), c["id"])
     return labels
 
 

@@ -106,6 +106,41 @@ def test_debug_views_inside_workspace(rt):
         rt.set_option("x3", 1)
 
 
+def test_debug_view_of_residual_block_outputs(rt):
+    """View 9 (ResUNet only): the stored output of block b = 0 .. 2 depth; an encoder's is the
+    skip half of its concat buffer (view 6), the others are dense buffers of their own; padded
+    widths (base 24 -> 32) keep the padded stride.  Refused for a network without residual
+    blocks and past the last block."""
+    import torch
+    from unet_hip import _lib
+    from unet_hip._lib import HipError
+    from unet_hip.runtime import UNetRuntime
+    N, H, W, D = 2, 32, 32, 2
+    for base, pad in ((64, 64), (24, 32)):
+        r = UNetRuntime("cuda:0", 1, 1, _lib.VARIANT_RES, base, D, _lib.MATH_F32)
+        nb = r.workspace_bytes(N, H, W, True)
+        ws = torch.empty(nb, dtype=torch.uint8)
+        spans = []
+        for b in range(2 * D + 1):
+            lvl = b if b <= D else 2 * D - b
+            v, off = r.debug_view(ws, N, H, W, True, 9, b)
+            rows, C = N * (H >> lvl) * (W >> lvl), pad << lvl
+            assert tuple(v.shape) == (rows, 2 * C if b < D else C) and off == 0, b
+            lo = v.data_ptr() - ws.data_ptr()
+            assert 0 <= lo and lo + 4 * v.numel() <= nb
+            if b < D:
+                cat, _ = r.debug_view(ws, N, H, W, True, 6, b)
+                assert cat.data_ptr() == v.data_ptr()
+            spans.append((lo, lo + 4 * v.numel()))
+        spans.sort()
+        assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), "block outputs overlap"
+        with pytest.raises(HipError):
+            r.debug_view(ws, N, H, W, True, 9, 2 * D + 1)
+    with pytest.raises(HipError):
+        rt.debug_view(torch.empty(rt.workspace_bytes(N, H, W, True), dtype=torch.uint8), N, H, W,
+                      True, 9, 0)
+
+
 def test_no_cpu_fallback():
     import torch
     import unet_hip

@@ -21,6 +21,27 @@ __device__ __forceinline__ f32x4 bn_dz4(f32x4 a, f32x4 d, f32x4 b, f32x4 y, f32x
     return r;
 }
 
+// The BN output a = fma(z, scale, shift) of a stored conv output z and the finalized BN affine,
+// and the BN -> ReLU branch a > 0 (models/mod.py:46-47), in one explicit rounding: the forward
+// consumers apply it and every backward site re-derives the branch from the same z, scale and
+// shift instead of reading a stored mask, so the two must round alike (one fma, never a rounded
+// product plus an add).  Every site that forms either goes through these -- the row-GEMM
+// loaders, the E_STORE_BN / E_RESID epilogues, max-pool forward and backward, the head, the
+// bf16 / x3 image passes, the fused pool / head dz passes, conv_first / res_first -- and the
+// tests read the same decision back as the sign of double(z) * double(scale) + double(shift).
+__device__ __forceinline__ float bn_act(float z, float scale, float shift) {
+    return __builtin_fmaf(z, scale, shift);
+}
+__device__ __forceinline__ bool bn_relu_on(float z, float scale, float shift) {
+    return bn_act(z, scale, shift) > 0.f;
+}
+__device__ __forceinline__ f32x4 bn_act4(f32x4 z, f32x4 scale, f32x4 shift) {
+    f32x4 r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = bn_act(z[j], scale[j], shift[j]);
+    return r;
+}
+
 // How the rows of a GEMM operand are gathered from an NHWC activation.
 //   G_CONV3: 3x3 / pad 1 taps on the row grid (tap t -> dy = t/3-1, dx = t%3-1),
 //            out-of-image taps read as zero (post-BN zero padding, models/model.py:36).

@@ -268,7 +268,7 @@ __device__ __forceinline__ void row_epilogue(const RowGemmArgs& p, f32x16 (&acc)
                 for (int r = 0; r < 16; ++r) {
                     float v = acc[mt][nt][r];
                     const float y = *(const float*)(urow(p.ey, p.ldey, p.offey, mt, r) + ly);
-                    if (emask && !(es * y + eb > 0.f)) v = 0.f;
+                    if (emask && !bn_relu_on(y, es, eb)) v = 0.f;
                     *(float*)(urow(p.out, p.ldo, p.ooff, mt, r) + lo) = v;
                     q[mt / 2][nt][0] += v;
                     q[mt / 2][nt][1] = __builtin_fma((double)v, (double)y, q[mt / 2][nt][1]);
@@ -281,7 +281,7 @@ __device__ __forceinline__ void row_epilogue(const RowGemmArgs& p, f32x16 (&acc)
                     if (m < p.M) {
                         float v = acc[mt][nt][r];
                         const float y = p.ey[(size_t)m * p.ldey + p.offey + n];
-                        if (emask && !(es * y + eb > 0.f)) v = 0.f;
+                        if (emask && !bn_relu_on(y, es, eb)) v = 0.f;
                         p.out[(size_t)m * p.ldo + p.ooff + n] = v;
                         q[mt / 2][nt][0] += v;
                         q[mt / 2][nt][1] = __builtin_fma((double)v, (double)y, q[mt / 2][nt][1]);
@@ -296,7 +296,7 @@ __device__ __forceinline__ void row_epilogue(const RowGemmArgs& p, f32x16 (&acc)
                 for (int r = 0; r < 16; ++r) {
                     const float y = yv[r];
                     float v = acc[mt][nt][r];
-                    if (emask && !(es * y + eb > 0.f)) v = 0.f;
+                    if (emask && !bn_relu_on(y, es, eb)) v = 0.f;
                     *(float*)(urow(p.out, p.ldo, p.ooff, mt, r) + lo) = v;
                     q[mt / 2][nt][0] += v;
                     q[mt / 2][nt][1] = __builtin_fma((double)v, (double)y, q[mt / 2][nt][1]);
@@ -316,7 +316,7 @@ __device__ __forceinline__ void row_epilogue(const RowGemmArgs& p, f32x16 (&acc)
                     const int m = m0 + wm * WM + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     const float y = yv[r];
                     float v = acc[mt][nt][r];
-                    if (emask && !(es * y + eb > 0.f)) v = 0.f;
+                    if (emask && !bn_relu_on(y, es, eb)) v = 0.f;
                     if (m < p.M) p.out[(size_t)m * p.ldo + p.ooff + n] = v;
                     v = m < p.M ? v : 0.f;
                     q[mt / 2][nt][0] += v;
@@ -457,7 +457,7 @@ __device__ __forceinline__ void row_epilogue(const RowGemmArgs& p, f32x16 (&acc)
                     if (m >= p.M) continue;
                     float* o = p.out + (size_t)m * p.ldo + p.ooff + n;
                     if constexpr (EMODE == E_RESID)
-                        *o = fmaxf(acc[mt][nt][r] + (es * p.ey[(size_t)m * p.ldey + p.offey + n] + eb),
+                        *o = fmaxf(acc[mt][nt][r] + bn_act(p.ey[(size_t)m * p.ldey + p.offey + n], es, eb),
                                    0.f);
                     else
                         *o += acc[mt][nt][r];
@@ -478,7 +478,7 @@ __device__ __forceinline__ void row_epilogue(const RowGemmArgs& p, f32x16 (&acc)
                     if (m >= p.M) continue;
                     float* o = p.out + (size_t)m * p.ldo + p.ooff + n;
                     if constexpr (EMODE == E_RESID)
-                        *o = fmaxf(acc[mt][nt][r] + (es * xv[r] + eb), 0.f);
+                        *o = fmaxf(acc[mt][nt][r] + bn_act(xv[r], es, eb), 0.f);
                     else
                         *o = xv[r] + acc[mt][nt][r];
                 }

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(T::THREADS, T::OCC) void rowgemm_kernel(RowGemmArgs
         for (int i = 0; i < AP; ++i) {
             f32x4 v = ra[i];
             if constexpr (AFFINE) {
-                v = v * rsc + rsh;
+                v = bn_act4(v, rsc, rsh);
                 if (ARELU && rrelu)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256, OCC) void rowgemm_direct_kernel(RowGemmArgs p)
             for (int mt = 0; mt < MT; ++mt) {
                 f32x4 v = ch.a[mt][g];
                 if constexpr (AFFINE) {
-                    v = v * sc + sh;
+                    v = bn_act4(v, sc, sh);
                     if (ARELU && ch.relu)
 #pragma unroll
                         for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(T::THREADS, T::OCC) void wgrad_kernel(WgradArgs p) 
         for (int i = 0; i < AP; ++i) {
             f32x4 v = ra[i];
             if constexpr (AFFINE) {
-                v = v * sc + sh;
+                v = bn_act4(v, sc, sh);
                 if (ARELU && arl)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(T::THREADS, T::OCC) void wgrad_row3_kernel(WgradArg
             if (AP * ARPP > AROWS && r >= AROWS) break;
             f32x4 v = ra[i];
             if constexpr (AFFINE) {
-                v = v * sc + sh;
+                v = bn_act4(v, sc, sh);
                 if (ARELU && arl)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
@@ -894,7 +894,7 @@ __global__ __launch_bounds__(T::THREADS, T::OCC) void wgradT_kernel(WgradArgs p)
             for (int u = 0; u < 4; ++u) {
                 v[u] = ra[i][u];
                 if constexpr (AFFINE) {
-                    v[u] = v[u] * sc + sh;
+                    v[u] = bn_act4(v[u], sc, sh);
                     if (ARELU && arl)
 #pragma unroll
                         for (int j = 0; j < 4; ++j) v[u][j] = fmaxf(v[u][j], 0.f);

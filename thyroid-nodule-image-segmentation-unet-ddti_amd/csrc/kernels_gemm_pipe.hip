@@ -160,7 +160,7 @@ __global__ __launch_bounds__(T::THREADS, T::OCC) void rowgemm_pipe_kernel(RowGem
             if constexpr (AFFINE) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float t = __builtin_fmaf(v[j], st.rsc[j], st.rsh[j]);
+                    const float t = bn_act(v[j], st.rsc[j], st.rsh[j]);
                     v[j] = (ARELU && st.rrelu) ? fmaxf(t, 0.f) : t;
                 }
             }

@@ -1199,7 +1199,7 @@ __global__ __launch_bounds__(256) void to_x3_kernel(const float* __restrict__ sr
                 for (int j = 0; j < 8; ++j) {
                     float t = v[i][j >> 2][j & 3];
                     if (scale) {
-                        t = __builtin_fmaf(sc[j], t, sh[j]);
+                        t = bn_act(t, sc[j], sh[j]);
                         if (c + j < relu) t = fmaxf(t, 0.f);
                     }
                     w[j] = t;
@@ -1310,7 +1310,7 @@ __global__ __launch_bounds__(256) void bn_dz_x3_kernel(const float* __restrict__
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             if (((wi[i][h] >> (8 * j)) & 0xFF) == (uint32_t)kk[i]) dv[i][h][j] += gp[i][h][j];
-                            if (pl.msc && !(__builtin_fmaf(msc[h][j], yv[i][h][j], msh[h][j]) > 0.f))
+                            if (pl.msc && !bn_relu_on(yv[i][h][j], msc[h][j], msh[h][j]))
                                 dv[i][h][j] = 0.f;
                         }
             }
@@ -1321,7 +1321,7 @@ __global__ __launch_bounds__(256) void bn_dz_x3_kernel(const float* __restrict__
                     for (int h = 0; h < 2; ++h)
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            const bool on = !hd.relu || __builtin_fmaf(yv[i][h][j], hs[h][j], hh[h][j]) > 0.f;
+                            const bool on = !hd.relu || bn_relu_on(yv[i][h][j], hs[h][j], hh[h][j]);
                             dv[i][h][j] = on ? dl[i] * hw[h][j] : 0.f;
                         }
             }

@@ -629,7 +629,7 @@ __device__ __forceinline__ void maxpool_px(const float* __restrict__ y, int ld, 
         const f32x4 yv = *(const f32x4*)(y + pin * ld + off + c);
         f32x4 v;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(yv[j], sc[j], sh[j]);
+        for (int j = 0; j < 4; ++j) v[j] = bn_act(yv[j], sc[j], sh[j]);
         if (pi.skip16 || pi.skip3) {  // the skip half's operand image: op(BN(y)) at this pixel
             f32x4 t = v;
             if (relu)
@@ -803,7 +803,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
                 for (int j = 0; j < 4; ++j) {
                     if (((bi >> (8 * j)) & 0xFF) == (uint32_t)k) v[j] += gp[j];
                     // (explicit fma: bn_dz_x3's fused pool source recomputes this mask, r05)
-                    if (mscale && !(__builtin_fmaf(ms[j], yv[j], mb[j]) > 0.f)) v[j] = 0.f;
+                    if (mscale && !bn_relu_on(yv[j], ms[j], mb[j])) v[j] = 0.f;
                 }
                 if (dout) *(f32x4*)(dout + pin * C + c) = v;  // (null: the dz pass recomputes it)
 #pragma unroll
@@ -978,7 +978,7 @@ __global__ __launch_bounds__(256) void bn_dz16_kernel(float* __restrict__ d, con
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             if (((wi[u][h] >> (8 * j)) & 0xFF) == (uint32_t)kk[u]) dv[u][h][j] += gp[u][h][j];
-                            if (pl.msc && !(__builtin_fmaf(msc[h][j], yv[u][h][j], msh[h][j]) > 0.f))
+                            if (pl.msc && !bn_relu_on(yv[u][h][j], msc[h][j], msh[h][j]))
                                 dv[u][h][j] = 0.f;
                         }
             }
@@ -989,7 +989,7 @@ __global__ __launch_bounds__(256) void bn_dz16_kernel(float* __restrict__ d, con
                     for (int h = 0; h < 2; ++h)
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            const bool on = !hd.relu || __builtin_fmaf(yv[u][h][j], hs[h][j], hh[h][j]) > 0.f;
+                            const bool on = !hd.relu || bn_relu_on(yv[u][h][j], hs[h][j], hh[h][j]);
                             dv[u][h][j] = on ? dl[u] * hw[h][j] : 0.f;
                         }
             }
@@ -1084,8 +1084,8 @@ __global__ __launch_bounds__(256) void to_bf16_kernel(const float* __restrict__ 
                 if (m >= P) break;
                 f32x4 v0 = v[u][0], v1 = v[u][1];
                 if (scale) {
-                    v0 = v0 * sc0 + sh0;
-                    v1 = v1 * sc1 + sh1;
+                    v0 = bn_act4(v0, sc0, sh0);
+                    v1 = bn_act4(v1, sc1, sh1);
                 }
                 if (c < relu) {
 #pragma unroll
@@ -1427,7 +1427,7 @@ __global__ void head_fwd_kernel(const float* __restrict__ y, int C, const float*
             f32x4 a = v[u];
             if (scale)  // explicit fma: the same activation as the backward's ReLU mask
 #pragma unroll
-                for (int j = 0; j < 4; ++j) a[j] = __builtin_fmaf(a[j], sc[j], sh[j]);
+                for (int j = 0; j < 4; ++j) a[j] = bn_act(a[j], sc[j], sh[j]);
             if (relu)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) a[j] = fmaxf(a[j], 0.f);
@@ -1471,7 +1471,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     auto one = [&](int m, const f32x4& yr, const float (&dl)[4]) {
         f32x4 v;  // explicit fma: bn_dz_x3's fused head source recomputes this mask (r05)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(yr[j], sc[j], sh[j]);
+        for (int j = 0; j < 4; ++j) v[j] = bn_act(yr[j], sc[j], sh[j]);
         if (relu)
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
@@ -1550,9 +1550,11 @@ __global__ void res_first_fwd_kernel(const float* __restrict__ x, const float* _
         const int64_t m = i / c4n;
         const float xv = x[m];
         const f32x4 zv = *(const f32x4*)(z + m * C + c);
-        f32x4 o = zv * *(const f32x4*)(sc + c) + *(const f32x4*)(sh + c) + xv * *(const f32x4*)(ws + c);
+        const f32x4 a = bn_act4(zv, *(const f32x4*)(sc + c), *(const f32x4*)(sh + c));
+        const f32x4 wv = *(const f32x4*)(ws + c);
+        f32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = fmaxf(o[j], 0.f);
+        for (int j = 0; j < 4; ++j) o[j] = fmaxf(__builtin_fmaf(xv, wv[j], a[j]), 0.f);
         *(f32x4*)(out + m * ldo + offo + c) = o;
     }
 }

@@ -2430,6 +2430,12 @@ int unet_debug_view(unet_ctx* c, int N, int H, int W, int training, int kind, in
             q = kind == 1 ? p.scale[index] : kind == 2 ? p.shift[index] : kind == 3 ? p.mean[index] : p.invstd[index];
             n = C;
         }
+    } else if (kind == 9) {  // residual network: the stored output of block `index`
+        if (!c->res || index < 0 || index > 2 * c->depth) return UNET_ERR_INVALID;
+        q = p.out[index];
+        l = p.ldout[index];
+        o = p.offout[index];
+        n = p.P[c->conv[2 * index].level] * l;
     } else {
         if (index < 0 || index >= c->depth) return UNET_ERR_INVALID;
         const int C = c->ch(index);
