@@ -180,10 +180,9 @@ class DistributedUNet:
         for _ in range(extra_scalar_reduces):
             z = torch.zeros(1, device=dev)
             dist.all_reduce(z, group=self.group)
-        if st.grad_arena is None:
-            st.grad_arena = torch.zeros_like(st.param_arena)
-        else:
-            st.grad_arena.zero_()
+        # an arena of its own, as a backward gets (a `.grad` the caller kept may alias the last)
+        st.grad_arena = None
+        st.grad_arena = torch.zeros_like(st.param_arena)
         for (p, _, _), g in zip(st.params, st.grad_views(st.grad_arena)):
             p.grad = g
         self._gathered_loss = True

@@ -2,7 +2,8 @@
 
 * ``UNetFunction``  - forward/backward of the whole encoder-decoder
   (models/model.py:53-73 forward, utils/trainer.py:91 backward).  Gradients land in one
-  flat arena laid out like the parameter arena; autograd receives views of it.
+  flat arena laid out like the parameter arena, a fresh one per backward; autograd receives
+  views of it.  A graph runs backward once: the backward consumes the forward's workspace.
 * ``SegLossFunction`` - the fused BCEWithLogits (mean) + Dice + FocalTversky statistics
   kernel (utils/trainer.py:85-87, models/loss.py:13-46), with an optional all-reduce of
   the 8 batch sums between the statistics and the finalize (data parallelism = the loss of
@@ -34,6 +35,10 @@ class UNetFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits):
         st = ctx.state
+        if ctx.ws is None:
+            raise RuntimeError("UNetFunction: the workspace of a training forward is consumed by "
+                               "its backward, so a graph runs backward once (retain_graph=True "
+                               "does not keep it); run the forward again for another backward")
         grads = st.grad_arena_for_backward()
         st.rt.backward(st.param_arena, dlogits.contiguous(), grads, ctx.ws)
         ctx.ws = None

@@ -20,6 +20,7 @@ num_batches_tracked) and the whole network runs as one native call.  Moving the 
 (``.to()``, ``.cuda()``) re-flattens lazily.  CPU tensors raise ``HipUnavailable``:
 there is no silent CPU fallback.
 """
+import copy
 import weakref
 
 import torch
@@ -112,15 +113,15 @@ class _ArenaState:
         self.native_version = None
 
     def grad_arena_for_backward(self):
-        # gradients are written with '=' semantics (zero_grad(set_to_none) is the reference's
-        # pattern, utils/trainer.py:81).  If .grad still aliases the arena (accumulation
-        # across backward calls), hand autograd a fresh arena so it can add.
-        if self.grad_arena is None:
-            self.grad_arena = torch.empty_like(self.param_arena)
-            return self.grad_arena
-        p0 = self.params[0][0]
-        if p0.grad is not None and p0.grad.data_ptr() == self.grad_arena.data_ptr():
-            return torch.empty_like(self.param_arena)
+        # gradients are written with '=' semantics, so every backward gets an arena nothing
+        # else can read: not the engine (it holds the views of an earlier application of the
+        # model in the same graph until it has added them up), not a `.grad` that is being
+        # accumulated into, not a `.grad` the caller kept over zero_grad(set_to_none=True).
+        # The state's own reference goes first: in the reference's pattern (utils/trainer.py:81,
+        # zero_grad(set_to_none=True) -> backward) it is the last one, and the caching allocator
+        # hands the same block back -- no new memory, no launch, no copy, no synchronisation.
+        self.grad_arena = None
+        self.grad_arena = torch.empty_like(self.param_arena)
         return self.grad_arena
 
     def grad_views(self, arena):
@@ -128,9 +129,45 @@ class _ArenaState:
 
 
 class _HipUNet(nn.Module):
-    """Arena management and the native forward shared by both reference networks."""
+    """Arena management and the native forward shared by both reference networks.
+
+    What autograd may do with the module:
+
+    * the model may be applied several times in one graph (two crops, a consistency loss):
+      every application's backward writes an arena of its own and the engine adds them;
+    * gradients accumulate over ``backward()`` calls as for any module, with either
+      ``zero_grad`` form; a ``.grad`` kept over ``zero_grad(set_to_none=True)`` keeps its
+      values.  After one backward from ``.grad is None`` (and after accumulating into that)
+      the ``.grad`` tensors are views of one flat arena laid out like the parameter arena,
+      which ``HipAdamW``'s one-launch step and ``DistributedUNet`` rely on;
+    * one backward per training forward: the forward's workspace is consumed by its backward,
+      a second one (``retain_graph=True``) raises ``RuntimeError``;
+    * no input gradient: a grad-enabled forward of an ``x`` that requires grad raises
+      ``ValueError`` instead of leaving ``x.grad`` empty;
+    * ``copy.deepcopy``, ``pickle`` and ``torch.save`` of the module give a model with
+      parameter and buffer tensors of its own and without the arenas, which re-flattens on
+      its first forward and finds the per-configuration runtime again."""
 
     _name = "UNet"
+
+    # ---------------------------------------------------------------- copies
+    def __deepcopy__(self, memo):
+        # the arenas hold the native handle (not copyable) and would tie the copy's tensors to
+        # this model's storage: the copy gets compact tensors of its own and no state
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for t in list(self.parameters()) + list(self.buffers()):
+            if id(t) not in memo:
+                c = t.detach().clone()
+                memo[id(t)] = nn.Parameter(c, t.requires_grad) if isinstance(t, nn.Parameter) else c
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = None if k == "_state" else copy.deepcopy(v, memo)
+        return new
+
+    def __getstate__(self):
+        # a pickled view carries its whole storage (the arena, once per parameter): pickle the
+        # compact tensors of a copy instead
+        return copy.deepcopy(self).__dict__
 
     def _native_cfg(self):
         """(in_channels, out_channels, variant, base_filters, depth, math) of the native graph."""
@@ -207,6 +244,9 @@ class _HipUNet(nn.Module):
             raise ValueError(f"expected (N, {self.in_channels}, H, W), got {tuple(x.shape)}")
         if x.device != st.param_arena.device:
             raise ValueError(f"input on {x.device}, model on {st.param_arena.device}")
+        if x.requires_grad and torch.is_grad_enabled():
+            raise ValueError(f"{self._name}: the native path computes no input gradient, x.grad "
+                             "would stay empty; pass x.detach() (or run under torch.no_grad())")
         x = x.contiguous().float()
         need_grad = self.training and torch.is_grad_enabled() and any(
             p.requires_grad for p, _, _ in st.params)
