@@ -72,8 +72,10 @@ def test_res_train_steps_match_golden(golden_dir):
             assert np.max(np.abs(g[idx].numpy() - samp[ti])) <= gtol * norms[ti], f"{p} {item[0]}"
         sd = m.state_dict()
         rm = torch.cat([sd[f"{n}.running_mean"].cpu() for n in names]).numpy()
+        rv = torch.cat([sd[f"{n}.running_var"].cpu() for n in names]).numpy()
         btol = 1e-4 if s == 0 else 1e-3
         np.testing.assert_allclose(rm, f[p + "running_mean"], rtol=btol, atol=btol)
+        np.testing.assert_allclose(rv, f[p + "running_var"], rtol=btol, atol=btol)
     # eval mode (Trainer.validate / test, utils/trainer.py:130,206-250): the oracle resynced
     # from this path's parameters and running statistics, at the north-star bar
     check_eval(m, MO.make_res_forward(3), x.cpu(), t.cpu())
