@@ -1,6 +1,6 @@
-"""Which GEMM kernels the bench.py configurations launch, and the small fp64-checked cases
-that stand for them (tests/test_gpu_kernel_coverage.py; helper of the tests, not a test;
-importable without a GPU).
+"""Which GEMM kernels the production configurations launch (what bench.py times, and the bf16
+residual network main.py trains), and the small fp64-checked cases that stand for them
+(tests/test_gpu_kernel_coverage.py; helper of the tests, not a test; importable without a GPU).
 
 runtime.hip chooses the kernel and tile of every conv / ConvT / skip GEMM from the shape and
 the CU count (x3_tile, x3_wgrad_cfg, rg16_tile, wgrad_cfg, pick_tile, wg16_tile,
@@ -19,7 +19,9 @@ W >> level relates to that count, because these kernels take another path for ea
 kernel gets "-".  Split-K counts, XCD block order and tile grouping are not in the label and
 not in the key (the bit-identity tests hold those).
 
-PRODUCTION: the configurations bench.py can time, at its own batch and image sizes.
+PRODUCTION: the configurations bench.py can time, at its own batch and image sizes, and the two
+bf16 ResUNet steps bench.py cannot (its --config res is f32 only): what main.py --model_type
+ResUNet --mfma bf16 trains and tools/res_bf16_time.py times.
 SMALL: the small cases; each forces the kernels under test through schedule options (the
 forcing rules of runtime.hip accept any tile that fits) at the smallest shape at which the
 kernel still meets its edges.
@@ -30,7 +32,10 @@ GEMM_FAMILIES = tuple(f"{a}_{b}" for a in ("conv", "convT", "skip") for b in ("f
 
 # bench.py: config 2 = UNet, bs 32 at 256^2; config 4 = ModUNet(128, 5), bs 8 at 512^2, --mfma
 # fp32 / bf16; --config res = ResUNet(--base, --depth), bs 16 at 512^2, f32 only (--mfma is
-# config 4's): the reference grid's bases at depth 4 and bench.py's own default (64, 5)
+# config 4's): the reference grid's bases at depth 4 and bench.py's own default (64, 5).
+# Not from bench.py: res64_bf16 / res64_d5_bf16, ResUNet(64, 4 / 5) with mfma_dtype="bf16" at
+# main.py's default batch and size (main.py --model_type ResUNet --mfma bf16; the two steps
+# tools/res_bf16_time.py times)
 PRODUCTION = [
     dict(id="c2", net="unet", base=64, depth=4, math="fp32", shape=(32, 256, 256)),
     dict(id="c4_fp32", net="mod", base=128, depth=5, math="fp32", shape=(8, 512, 512)),
@@ -41,6 +46,8 @@ PRODUCTION = [
     dict(id="res48", net="res", base=48, depth=4, math="fp32", shape=(16, 512, 512)),
     dict(id="res64", net="res", base=64, depth=4, math="fp32", shape=(16, 512, 512)),
     dict(id="res64_d5", net="res", base=64, depth=5, math="fp32", shape=(16, 512, 512)),
+    dict(id="res64_bf16", net="res", base=64, depth=4, math="bf16", shape=(16, 512, 512)),
+    dict(id="res64_d5_bf16", net="res", base=64, depth=5, math="bf16", shape=(16, 512, 512)),
 ]
 
 MAX_PIXELS = 128 * 512  # per sample
@@ -157,6 +164,24 @@ SMALL = [
           "256x128 halo tile with the residual epilogues (E_ADD dgrad)", x3_tile=4),
     _case("res64_default", "res", 64, 3, "fp32", (2, 64, 64),
           "the default rule at a small grid (shape of test_res_full_grads_vs_oracle)"),
+    # ---- models/mod.py ResUNet, bf16: bf16-operand oracle of tests/res_bf16_ref.py
+    _case("res64_bf16_default", "res", 64, 3, "bf16", (2, 64, 64),
+          "register-staged bf16 tiles of the 64-channel level, f32 first block, 128x128 LDS-DMA "
+          "tile (small grid) with the residual epilogues (shape of test_res_bf16_matches_bf16_oracle)"),
+    _case("res64_bf16_halo256", "res", 64, 4, "bf16", (1, 16, 512),
+          "256x256 halo tile with the E_ADD dgrad: gt / eq / lt; tap-row wgrad gt", rg16_tile=19),
+    _case("res64_bf16_halo512", "res", 64, 4, "bf16", (1, 16, 512),
+          "512x128 halo tile on the 128-output level: eq at W = 512, lt below", rg16_tile=20),
+    _case("res64_bf16_halo256_n3", "res", 64, 4, "bf16", (3, 32, 256),
+          "256x256 halo tile over sample borders; W = 32 and W = 16 rows of the tap-row wgrad",
+          rg16_tile=19),
+    _case("res64_bf16_256x128", "res", 64, 3, "bf16", (1, 48, 80),
+          "256x128 one-tap tile ending past M: skip forward (E_RESID), skip dgrad (E_STORE), "
+          "conv1 dgrad (E_ADD)", rg16_tile=2),
+    _case("res64_bf16_256x256", "res", 64, 3, "bf16", (1, 48, 80),
+          "256x256 one-tap tile ending past M (128-output GEMMs: 128x128)", rg16_tile=4),
+    _case("res64_bf16_512x128", "res", 64, 3, "bf16", (3, 16, 48),
+          "512x128 one-tap tile ending past M, over sample borders", rg16_tile=6),
 ]
 
 

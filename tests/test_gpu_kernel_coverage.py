@@ -1,17 +1,19 @@
-"""Every GEMM kernel and tile a bench.py configuration launches is tied to a small case that
-is checked against the fp64 oracle (tests/kernel_cases.py: PRODUCTION, SMALL, key).
+"""Every GEMM kernel and tile a production configuration launches -- the bench.py
+configurations and the bf16 ResUNet steps main.py trains -- is tied to a small case that is
+checked against the fp64 oracle (tests/kernel_cases.py: PRODUCTION, SMALL, key).
 
 test_small_case_vs_fp64 runs one training step per small case with per-launch timing on and
 judges it against the fp64 oracle by the project's methods and bars (the masked-fp64
 step of tests/test_gpu_x3.py for models/model.py UNet; the fp32-oracle envelope of
 test_mod_narrow_full_grads_vs_fp64 / test_res_full_grads_vs_oracle for the f32 mod.py networks;
-the bf16-operand oracle and envelope of test_mod_bf16_matches_bf16_oracle for bf16; for every
+the bf16-operand oracle and envelope of test_mod_bf16_matches_bf16_oracle for bf16, with
+tests/res_bf16_ref.py as the residual network's bf16-operand oracle; for every
 mod.py case also the branch-pinned fp64 check of tests/masked.py, whose bars are ~100x / ~10x
 below those envelopes).  Only a
 case that passed lends its launch keys to the coverage; agreement between two tiles counts for
 nothing here.
 
-test_production_kernels_are_covered then runs one step of each bench.py configuration with
+test_production_kernels_are_covered then runs one step of each production configuration with
 default options, takes the launch labels only, and fails for every GEMM key no passed small
 case launched -- so a kernel or tile that becomes a default without an fp64-checked small case
 fails the suite.  test_coverage_table_written records the table in
@@ -27,6 +29,7 @@ import torch
 
 import kernel_cases as KC
 import masked as MK
+import res_bf16_ref as RB
 import test_gpu_x3 as TX
 from _helpers import grad_errors, hip_mod_model, hip_model, inputs, norm_rel, options, rel_max
 from oracle import mod_ref_cpu as MO
@@ -73,7 +76,10 @@ def _oracle_fns(c):
     if c["net"] == "mod":
         return (lambda s: MO.make_params(s, b, d), lambda: MO.init_buffers(b, d),
                 lambda P, B, x, t, bf16=False: MO.train_step(P, B, None, x, t, depth=d, bf16=bf16))
-    assert c["net"] == "res" and c["math"] == "fp32"
+    assert c["net"] == "res" and c["math"] in ("fp32", "bf16"), (c["net"], c["math"])
+    if c["math"] == "bf16":  # with bf16=False the helper is MO.res_train_step op for op
+        return (lambda s: MO.res_make_params(s, b, d), lambda: MO.res_init_buffers(b, d),
+                lambda P, B, x, t, bf16=False: RB.res_train_step(P, B, None, x, t, depth=d, bf16=bf16))
     return (lambda s: MO.res_make_params(s, b, d), lambda: MO.res_init_buffers(b, d),
             lambda P, B, x, t, bf16=False: MO.res_train_step(P, B, None, x, t, depth=d))
 
@@ -228,9 +234,10 @@ def _require_small_cases():
 
 @pytest.mark.parametrize("config", [c["id"] for c in KC.PRODUCTION])
 def test_production_kernels_are_covered(config):
-    """One default-option training step of a bench.py configuration at bench.py's own batch and
-    image size; labels only.  Every GEMM key it launches must have been launched by a small case
-    that passed its fp64 check, and so must every elementwise family."""
+    """One default-option training step of a production configuration at its own batch and
+    image size (bench.py's, main.py's for the bf16 residual network); labels only.  Every GEMM
+    key it launches must have been launched by a small case that passed its fp64 check, and so
+    must every elementwise family."""
     _require_small_cases()
     import unet_hip.runtime as RT
     c = KC.by_id(KC.PRODUCTION)[config]
@@ -278,7 +285,7 @@ def test_coverage_table_written():
             rows.setdefault(k, []).append(cfg)
     lines = ["# Written by tests/test_gpu_kernel_coverage.py::test_coverage_table_written.",
              "# GEMM launch keys (family, kernel_tile, row class: tests/kernel_cases.py key) of one",
-             "# default-option training step of every bench.py configuration, and the small",
+             "# default-option training step of every production configuration, and the small",
              "# fp64-checked cases (tests/kernel_cases.py SMALL) that launch the same key.",
              f"# {'family':12s} {'kernel_tile':24s} {'rows':4s}  configurations <- small cases"]
     for k in sorted(rows):

@@ -3,7 +3,7 @@ ReLU / max-pool branches (tests/masked.py), at the edges where kernels go wrong:
 no multiple of 64 (1x48x80), odd batch with a 2x2 bottleneck (3x32x32 at depth 4), padded
 widths (base 24 / 48: padded channels must stay out of every gradient), negative BN gammas,
 depth 1, and the bf16 paths (mod (64, 3), (128, 3); ResUNet base 64 -- register-staged level 0
--- and base 128).  The f32 cases run on the x3 kernels and on the f32-MFMA kernels (x3 = 0).
+--, base 128 and base 256, the widest documented, at depth 2).  The f32 cases run on the x3 kernels and on the f32-MFMA kernels (x3 = 0).
 
 Compared per case with the fp64 step on the device's branches (bf16: the bf16-operand oracle in
 fp64): logits norm-relative; per-tensor norm-relative and max|a - ref| / max|ref| gradient
@@ -52,6 +52,7 @@ BF16 = [
     _case("mod64_bf16_48x80", "mod", "bf16", 64, 3, (1, 48, 80)),
     _case("res64_bf16", "res", "bf16", 64, 3, (2, 64, 64)),
     _case("res128_bf16", "res", "bf16", 128, 3, (2, 64, 64)),
+    _case("res256_bf16", "res", "bf16", 256, 2, (2, 32, 32)),
 ]
 _RAN = set()
 

@@ -70,9 +70,41 @@ def test_production_is_what_bench_times():
     shapes = {c["id"]: c["shape"] for c in KC.PRODUCTION}
     assert shapes["c2"] == (32, 256, 256)
     assert shapes["c4_fp32"] == shapes["c4_bf16"] == (8, 512, 512)
-    res = [c for c in KC.PRODUCTION if c["net"] == "res"]
+    res = [c for c in KC.PRODUCTION if c["net"] == "res" and c["math"] == "fp32"]
     assert {(c["base"], c["depth"]) for c in res} >= {(b, 4) for b in (16, 24, 32, 48, 64)}
-    assert all(c["shape"] == (16, 512, 512) and c["math"] == "fp32" for c in res)
+    assert all(c["shape"] == (16, 512, 512) for c in res)
+    # bench.py's --config res is f32 only: every bf16 residual row is main.py's, not bench.py's
+    assert "ResUNet(1, 1, base_filters=args.base, depth=args.depth)" in src
+
+
+def test_production_has_the_bf16_residual_steps_main_trains():
+    """main.py --model_type ResUNet --mfma bf16 at its defaults (base 64, depth 5, bs 16, 512^2)
+    and the two steps tools/res_bf16_time.py times (read from their sources)."""
+    rows = {c["id"]: c for c in KC.PRODUCTION if c["net"] == "res" and c["math"] == "bf16"}
+    assert set(rows) == {"res64_bf16", "res64_d5_bf16"}
+    assert (rows["res64_bf16"]["base"], rows["res64_bf16"]["depth"]) == (64, 4)
+    assert (rows["res64_d5_bf16"]["base"], rows["res64_d5_bf16"]["depth"]) == (64, 5)
+    assert all(c["shape"] == (16, 512, 512) for c in rows.values())
+    tool = open(os.path.join(REPO, "tools", "res_bf16_time.py")).read()
+    assert "base_filters=64, depth=depth, mfma_dtype=mfma" in tool and "for depth in (4, 5):" in tool
+    assert 'add_argument("--batch", type=int, default=16)' in tool
+    assert 'add_argument("--size", type=int, default=512)' in tool
+
+
+def test_bf16_residual_small_cases():
+    """The res / bf16 small cases force each LDS-DMA tile the production steps take (one-tap 2,
+    4, 6; halo 19, 20), keep one on the default rule, and meet a sample border on a halo tile."""
+    rb = [c for c in KC.SMALL if c["net"] == "res" and c["math"] == "bf16"]
+    assert {c["opts"].get("rg16_tile", -1) for c in rb} == {-1, 2, 4, 6, 19, 20}
+    assert all(c["base"] == 64 and set(c["opts"]) <= {"rg16_tile"} for c in rb)
+    assert any(c["shape"][0] == 3 and c["opts"].get("rg16_tile") == 19 for c in rb)
+    for tile, rows, want in ((19, 256, {"lt", "eq", "gt"}), (20, 512, {"lt", "eq"})):
+        got = set()
+        for c in rb:
+            if c["opts"].get("rg16_tile") == tile:
+                got |= {"lt" if w < rows else "eq" if w == rows else "gt"
+                        for w in (c["shape"][2] >> l for l in range(c["depth"] + 1)) if w >= 16}
+        assert got == want, (tile, got)
 
 
 @pytest.mark.parametrize("case", [c["id"] for c in KC.SMALL])

@@ -1,14 +1,19 @@
 """The branch-pinned fp64 method of tests/masked.py, checked on the CPU: the hooks reproduce a
 run from its own recorded decisions bit for bit, pinning removes the ReLU-flip slack from the
 fp32-vs-fp64 spread, and the comparison the GPU tests use fails gradients with one seeded fault
-each that the unpinned bars (floor 1e-2; 2x the unpinned bf16 spread) let through."""
+each that the unpinned bars (floor 1e-2; 2x the unpinned bf16 spread) let through.  For the bf16
+residual network the faults are those one wrong tile edge produces: a lost K chunk of a weight
+gradient, a lost image column, a residual add from the neighbouring row."""
 import os
 
 import pytest
 import torch
 
 import masked as MK
+import res_bf16_ref as RB
 from _helpers import inputs, norm_rel
+from oracle import mod_ref_cpu as MO
+from oracle import unet_ref_cpu as O
 
 
 @pytest.fixture(autouse=True, scope="module")
@@ -163,3 +168,105 @@ def test_seeded_bf16_fault_fails_the_pinned_bars():
     print(f"channel zeroed in {name}: unpinned error {worst:.2e}, old envelope {old:.2e}, pinned "
           f"bar {s['bar']['w_norm']:.2e}")
     assert worst <= old
+
+
+# ---- the bf16 residual network: faults of the size one wrong tile edge produces.  ResUNet(64, 4)
+# at 2x32x64: 2 x 16 x 32 = 1024 pixels at level 1, 2 x 8 x 16 = 256 at level 2.
+RESBF = _case("res", "bf16", 64, 4, (2, 32, 64))
+CHUNK_CONV = (5, "encoders.2.conv.3.weight")  # MO._conv3 call 2 b + 1 of block b = 2: level 2
+COLUMN_SKIP = (7, 0, 5)                       # RB._skip call of block 7 (decoders.2, level 1), sample, column
+RESID_BLOCK = ("decoders.2", 256)             # the block whose add is faulted, first row of the group
+
+
+def _rows(t):
+    """NCHW as the [pixels][channels] rows the GEMM kernels walk (n, h, w raster): a view."""
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+
+
+class _DropColumn(torch.autograd.Function):
+    """Identity whose backward loses image column `col` of sample `n`."""
+
+    @staticmethod
+    def forward(ctx, x, n, col):
+        ctx.at = (n, col)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.clone()
+        g[ctx.at[0], :, :, ctx.at[1]] = 0
+        return g, None, None
+
+
+def _seeded_res_bf16(s, fault, monkeypatch):
+    """The fp32 bf16-operand oracle's step on s's branches with one fault seeded:
+    "chunk": 64 consecutive pixels (one K chunk of the tap-row kernel) left out of the weight-
+        gradient sum of CHUNK_CONV, the products on the operands the oracle rounds;
+    "column": one image column of one sample zero in the output gradient COLUMN_SKIP's 1x1 GEMM
+        reads in backward (both its weight and its input gradient lose it);
+    "resid": the residual add of RESID_BLOCK takes the BN output of pixel p + 1 for the 128
+        GEMM rows p = first .. first + 127 (the forward value only: the backward of a kernel
+        with that fault knows nothing of it)."""
+    seen, calls = {}, dict(conv=0, skip=0)
+    conv3, skip, bn = MO._conv3, RB._skip, O._bn
+
+    def conv3_(x, w, bf16):
+        y = conv3(x, w, bf16)
+        if calls["conv"] == CHUNK_CONV[0]:
+            seen["x"], seen["shape"] = x.detach(), w.shape
+            y.register_hook(lambda g: seen.__setitem__("g", g.detach()))
+        calls["conv"] += 1
+        return y
+
+    def skip_(x, w, bf16):
+        y = skip(x, w, bf16)
+        if calls["skip"] == COLUMN_SKIP[0]:
+            y = _DropColumn.apply(y, *COLUMN_SKIP[1:])
+        calls["skip"] += 1
+        return y
+
+    def bn_(x, P, B, name, training):
+        y = bn(x, P, B, name, training)
+        if name == f"{RESID_BLOCK[0]}.conv.4":
+            rows = _rows(y.detach())
+            d = torch.zeros_like(rows)
+            p0 = RESID_BLOCK[1]
+            d[p0:p0 + 128] = rows[p0 + 1:p0 + 129] - rows[p0:p0 + 128]
+            N, C, H, W = y.shape
+            y = y + d.reshape(N, H, W, C).permute(0, 3, 1, 2)
+        return y
+
+    if fault == "chunk":
+        monkeypatch.setattr(MO, "_conv3", conv3_)
+    elif fault == "column":
+        monkeypatch.setattr(RB, "_skip", skip_)
+    else:
+        monkeypatch.setattr(O, "_bn", bn_)
+    r = MK.step(RESBF, s["P"], s["x"], s["t"], False, s["br"])
+    monkeypatch.undo()
+    if fault == "chunk":
+        g = MO._rnd(seen["g"])
+        keep = torch.zeros(g.shape[0] * g.shape[2] * g.shape[3], 1)
+        keep[128:192] = 1
+        N, C, H, W = g.shape
+        g = g * keep.reshape(N, H, W, 1).permute(0, 3, 1, 2)
+        lost = torch.nn.grad.conv2d_weight(MO._rnd(seen["x"]), seen["shape"], g, padding=1)
+        assert float(lost.norm()) > 0
+        r["grads"][CHUNK_CONV[1]] = r["grads"][CHUNK_CONV[1]] - lost
+    return r
+
+
+@pytest.mark.parametrize("fault", ["chunk", "column", "resid"])
+def test_seeded_res_bf16_tile_edge_fault_fails_the_pinned_bars(fault, monkeypatch):
+    """ResUNet(64, 4), bf16 operands, 2x32x64, reference: the pinned fp64 step.  The fp32
+    oracle's own result passes masked.check at the bars of masked.bars; the same result with one
+    fault of the size a wrong tile edge produces fails it -- a 64-pixel chunk missing from a
+    level-2 3x3 weight gradient (of 256 pixels), one image column of one sample missing from a
+    level-1 skip GEMM's output gradient (of 64 columns), the residual add of one 128-row group
+    taken from the neighbouring pixel (of 1024 rows).  A fault that passed would mean the shape
+    is too large for its bars: shrink the shape, the bars are masked.bars' own."""
+    s = _shared(RESBF)
+    MK.check(s["r32"]["grads"], s["r32"]["logits"], s["r64"], s["bar"], "cpu_res_bf16")
+    bad = _seeded_res_bf16(s, fault, monkeypatch)
+    with pytest.raises(AssertionError, match="bar"):
+        MK.check(bad["grads"], bad["logits"], s["r64"], s["bar"], f"cpu_res_bf16_{fault}")
