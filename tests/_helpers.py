@@ -68,7 +68,13 @@ def check_eval(m, forward_fn, x, t, tol=1e-4):
     (running-stat BN) logits at the north-star bar, the test masks (utils/trainer.py:217
     sigmoid > 0.5, bit-exact outside the forward error band) and the confusion counts of
     unet_mask_counts vs the reference's counting (utils/trainer.py:219-242: targets
-    astype(uint8), TP/FP/FN/TN over every pixel).  Returns the near-boundary mask flips."""
+    astype(uint8), TP/FP/FN/TN over every pixel).  Returns the near-boundary mask flips.
+
+    Its callers run it at small shapes under the default options, on the logits only, with
+    buffers a step or two from their initial values: it reaches no forced tile, no halo row
+    class and no layer below the logits.  tests/test_gpu_eval_coverage.py holds the eval
+    forward's kernels, tile by tile and layer by layer, to the fp64 oracle with trained-like
+    buffers; this check asserts nothing less for it."""
     dev = next(m.parameters()).device
     Pc = {k: v.detach().cpu().clone() for k, v in m.named_parameters()}
     Bc = {k: v.detach().cpu().clone() for k, v in m.named_buffers()}

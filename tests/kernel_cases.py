@@ -25,6 +25,7 @@ ResUNet --mfma bf16 trains and tools/res_bf16_time.py times.
 SMALL: the small cases; each forces the kernels under test through schedule options (the
 forcing rules of runtime.hip accept any tile that fits) at the smallest shape at which the
 kernel still meets its edges.
+INFERENCE / SMALL_EVAL: the same pair for the eval-mode forward (tests/test_gpu_eval_coverage.py).
 """
 import re
 
@@ -49,6 +50,31 @@ PRODUCTION = [
     dict(id="res64_bf16", net="res", base=64, depth=4, math="bf16", shape=(16, 512, 512)),
     dict(id="res64_d5_bf16", net="res", base=64, depth=5, math="bf16", shape=(16, 512, 512)),
 ]
+
+
+def _single(id, shape):
+    c = dict(next(c for c in PRODUCTION if c["id"] == id))
+    c.update(id=f"{id}_n1", shape=shape)
+    return c
+
+
+# The eval-mode forwards production runs (Trainer.validate / Trainer.test, main.py --mode test,
+# unet_hip.tta_predict): every PRODUCTION entry at its own shape (validation and test run at the
+# training batch and size), and the single-image / partial-last-batch forward at N = 1, where the
+# block-count thresholds of x3_tile / rg16_tile choose other tiles.  tta_predict runs the model
+# per view at the caller's batch: no shape of its own.
+INFERENCE = [dict(c) for c in PRODUCTION] + [
+    _single("res64", (1, 512, 512)),
+    _single("res64_bf16", (1, 512, 512)),
+    _single("res64_d5_bf16", (1, 512, 512)),
+    _single("c2", (1, 256, 256)),
+    _single("c4_bf16", (1, 512, 512)),
+]
+
+# families only a backward launches: no eval forward may show one
+BACKWARD_FAMILIES = tuple(f for f in GEMM_FAMILIES if not f.endswith("_fwd")) + (
+    "bn_bwd_reduce", "bn_bwd_finalize", "bn_dz", "bias_grad", "wgrad_reduce", "conv_first_wgrad",
+    "pad_compact", "res_bwd_prep", "head_bwd", "head_grad", "maxpool_bwd")
 
 MAX_PIXELS = 128 * 512  # per sample
 MAX_N = 3
@@ -187,3 +213,60 @@ SMALL = [
 
 def by_id(cases):
     return {c["id"]: c for c in cases}
+
+
+def _eval(id, note, **kw):
+    """The SMALL case `id` run in eval mode (forward only): same network, shape and options,
+    which reproduce its forward keys -- the tile rules (x3_tile, rg16_tile, pick_tile) read the
+    shape and the options, not the mode.  pseed / xseed: parameter and input seeds (7 / 33, the
+    coverage test's, unless the meaningful-input condition of tests/test_eval_ref_cpu.py asks
+    for others)."""
+    c = dict(by_id(SMALL)[id])
+    c.update(note=note, pseed=kw.pop("pseed", 7), xseed=kw.pop("xseed", 33))
+    assert not kw
+    return c
+
+
+# Eval-mode small cases (tests/test_gpu_eval_coverage.py), one per distinct set of forward keys
+# of a network and math; where two SMALL cases launch the same forward keys the one with N = 3
+# stays (it also serves the sample-independence test).  Left out for that reason: unet_wtile64
+# (a weight-gradient option; forward keys of unet_default), unet_halo128 (unet_halo128_n3),
+# res64_bf16_halo256 (res64_bf16_halo256_n3).  Eval chooses no tile of its own: the keys of every
+# INFERENCE entry, N = 1 included (128x128 one-tap tiles below 256 blocks, the 128x64 halo tile
+# of a single 512^2 image's level 0), are forward keys of these cases.  What differs in eval is
+# the operand writers behind the same GEMM: every conv and ConvT reads an image prep16 / prep_x3
+# wrote into the one scratch image, the whole concat included; the notes name what each case
+# adds there.  Factor of the f32 bars: 4x the fp32 CPU oracle's deviation from fp64 per layer
+# (no case sets x3 = 0, whose factor is 12x); NARROW_12X names the levels of the narrow
+# networks (f32 MFMA kernels under x3 = 1) that take 12x instead -- none.
+NARROW_12X = ()   # (case id, level)
+SMALL_EVAL = [
+    _eval("unet_default", "default rule, small grid; whole-concat prep_x3 ([up, skip] order, ReLU -> BN)"),
+    _eval("unet_halo256", "256x128 halo tile on the scratch image: eq / lt"),
+    _eval("unet_halo256_n3", "256x128 halo tile over sample borders, 2 x 16 pixels at the deepest level"),
+    _eval("unet_halo128_n3", "128x64 halo tile: gt / eq / lt, over sample borders, W = 16 rows"),
+    _eval("unet_onetap256", "256x128 / 256x64 one-tap tiles ending past M"),
+    _eval("mod128_default", "default rule; whole-concat prep with the skip-half affine and ReLU span"),
+    _eval("mod128_halo256", "256x128 halo tile: gt / eq / lt; the max-pool stores into the scratch image"),
+    _eval("mod128_halo256_n3", "256x128 halo tile over sample borders, 4 x 16 pixels at the deepest level"),
+    _eval("mod128_onetap256", "256x128 one-tap tile ending past M"),
+    _eval("mod128_bf16_default", "128x128 LDS-DMA tile; prep16 of every image, f32 pooled tensor"),
+    _eval("mod128_bf16_halo256", "256x256 halo tile on the scratch image: eq / lt"),
+    _eval("mod128_bf16_halo512", "512x128 halo tile: eq / lt"),
+    _eval("mod128_bf16_halo256_n3", "256x256 halo tile over sample borders"),
+    _eval("mod128_bf16_256x128", "256x128 one-tap tile ending past M"),
+    _eval("mod128_bf16_256x256", "256x256 one-tap tile ending past M"),
+    _eval("mod128_bf16_512x128", "512x128 one-tap tile ending past M, over sample borders"),
+    _eval("res16_default", "padded 16 -> 32 (pbn expansion of the running buffers), f32 MFMA tiles, skip GEMMs"),
+    _eval("res24_default", "padded 24 / 48 / 96"),
+    _eval("res32_halo128", "128x64 halo tile on the 64-channel level next to the 32-channel level"),
+    _eval("res48_default", "padded 48 -> 64, odd N, over sample borders"),
+    _eval("res64_halo256", "256x128 halo tile with the residual epilogue (E_RESID from eval scale / shift)"),
+    _eval("res64_default", "default rule, small grid"),
+    _eval("res64_bf16_default", "register-staged bf16 tiles, f32 first block, r16 shared by conv1 and the skip GEMM"),
+    _eval("res64_bf16_halo512", "512x128 halo tile: lt"),
+    _eval("res64_bf16_halo256_n3", "256x256 halo tile over sample borders"),
+    _eval("res64_bf16_256x128", "256x128 one-tap tile ending past M: conv, ConvT and skip forward"),
+    _eval("res64_bf16_256x256", "256x256 one-tap tile ending past M"),
+    _eval("res64_bf16_512x128", "512x128 one-tap tile ending past M, over sample borders"),
+]

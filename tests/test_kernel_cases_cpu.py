@@ -54,7 +54,7 @@ def test_levels():
 
 
 def test_ids_unique_and_known_networks():
-    for cases in (KC.SMALL, KC.PRODUCTION):
+    for cases in (KC.SMALL, KC.PRODUCTION, KC.SMALL_EVAL, KC.INFERENCE):
         ids = [c["id"] for c in cases]
         assert len(ids) == len(set(ids))
         for c in cases:
@@ -107,9 +107,9 @@ def test_bf16_residual_small_cases():
         assert got == want, (tile, got)
 
 
-@pytest.mark.parametrize("case", [c["id"] for c in KC.SMALL])
+@pytest.mark.parametrize("case", [c["id"] for c in KC.SMALL] + [c["id"] + "@eval" for c in KC.SMALL_EVAL])
 def test_small_shape_rules(case):
-    c = KC.by_id(KC.SMALL)[case]
+    c = KC.by_id(KC.SMALL_EVAL if case.endswith("@eval") else KC.SMALL)[case.partition("@")[0]]
     N, H, W = c["shape"]
     q = max(16, 2 ** c["depth"])
     assert H % q == 0 and W % q == 0, (H, W, q)
@@ -120,15 +120,15 @@ def test_small_options_are_library_options():
     text = open(os.path.join(REPO, "include", "unet_hip.h")).read()
     block = text[text.index("Names (runtime.hip OPTION_TABLE"):text.index("Set them between steps")]
     names = set(re.findall(r"[a-z][a-z0-9_]+", block.split("\n", 1)[1].replace("*", " ")))
-    used = {k for c in KC.SMALL for k in c["opts"]}
+    used = {k for c in KC.SMALL + KC.SMALL_EVAL for k in c["opts"]}
     assert used and used <= names, used - names
 
 
-def _halo_classes(option, tile, rows):
+def _halo_classes(option, tile, rows, cases=None):
     """Row classes the levels of the small cases that force `tile` meet (3x3 levels of at
     least 16 pixels per row, as the halo kernels require)."""
     out = set()
-    for c in KC.SMALL:
+    for c in KC.SMALL if cases is None else cases:
         if c["opts"].get(option) != tile:
             continue
         for level in range(c["depth"] + 1):
@@ -154,3 +154,62 @@ def test_edge_classes_occur():
     assert any((w >> c["depth"]) == 16 and (h >> c["depth"]) % 2 == 0 and c["opts"]
                for c in KC.SMALL for _, h, w in [c["shape"]])  # W = 16 at the deepest level
     assert {16, 24, 48} <= {c["base"] for c in KC.SMALL}        # padded channels
+
+
+def test_inference_is_production_plus_single_images():
+    """Validation and test run at the training batch and size; the single-image / partial-batch
+    forward at N = 1 of the networks main.py and bench.py's headline configurations run."""
+    n = len(KC.PRODUCTION)
+    assert KC.INFERENCE[:n] == KC.PRODUCTION
+    single = {c["id"]: c for c in KC.INFERENCE[n:]}
+    assert {k: v["shape"] for k, v in single.items()} == {
+        "res64_n1": (1, 512, 512), "res64_bf16_n1": (1, 512, 512), "res64_d5_bf16_n1": (1, 512, 512),
+        "c2_n1": (1, 256, 256), "c4_bf16_n1": (1, 512, 512)}
+    prod = KC.by_id(KC.PRODUCTION)
+    for cid, c in single.items():
+        p = prod[cid[:-3]]
+        assert all(c[k] == p[k] for k in ("net", "base", "depth", "math"))
+
+
+def test_eval_cases_are_small_cases_in_eval_mode():
+    """Every eval case is a SMALL case (same network, shape and options: the forward tile rules
+    read nothing else), with a note of its own and the coverage test's seeds unless the table
+    says otherwise; the three left out share their forward keys with one that stays."""
+    small = KC.by_id(KC.SMALL)
+    for c in KC.SMALL_EVAL:
+        s = small[c["id"]]
+        assert all(c[k] == s[k] for k in ("net", "base", "depth", "math", "shape", "opts"))
+        assert c["note"] and isinstance(c["pseed"], int) and isinstance(c["xseed"], int)
+    assert len(KC.SMALL_EVAL) < len(KC.SMALL)
+    assert set(small) - {c["id"] for c in KC.SMALL_EVAL} == {"unet_wtile64", "unet_halo128", "res64_bf16_halo256"}
+    for case, level in KC.NARROW_12X:
+        c = KC.by_id(KC.SMALL_EVAL)[case]
+        assert c["math"] == "fp32" and (c["base"] << level) % 64 and 0 <= level <= c["depth"]
+
+
+def test_eval_edge_classes_occur():
+    """gt / eq / lt of both x3 halo tiles and eq / lt of both bf16 halo tiles (level 0 of the
+    128-base network takes the 128-output tile, so 256x256 is never "gt" in a forward), tiles
+    ending past M, sample borders and 16-pixel rows, padded channels -- in eval mode."""
+    ev = KC.SMALL_EVAL
+    assert _halo_classes("x3_tile", 4, 256, ev) == {"lt", "eq", "gt"}
+    assert _halo_classes("x3_tile", 6, 128, ev) == {"lt", "eq", "gt"}
+    assert _halo_classes("rg16_tile", 19, 256, ev) >= {"lt", "eq"}
+    assert _halo_classes("rg16_tile", 20, 512, ev) == {"lt", "eq"}
+    shapes = {c["shape"] for c in ev}
+    assert {(1, 16, 512), (1, 48, 80), (3, 32, 256), (3, 32, 128), (3, 16, 48)} <= shapes
+    assert {16, 24, 48} <= {c["base"] for c in ev}
+    for net, math in (("unet", "fp32"), ("mod", "fp32"), ("mod", "bf16"), ("res", "fp32"), ("res", "bf16")):
+        mine = [c for c in ev if (c["net"], c["math"]) == (net, math)]
+        assert any(c["shape"][0] == 3 for c in mine) and any(not c["opts"] for c in mine), (net, math)
+
+
+def test_backward_families_are_no_forward_families():
+    assert all(f.endswith(("dgrad", "wgrad")) for f in KC.BACKWARD_FAMILIES if f in KC.GEMM_FAMILIES)
+    forward = {"bn_finalize", "bn_stats_reduce", "prep16", "prep_x3", "pack", "fill", "copy_x", "conv_first_fwd",
+               "res_out", "maxpool_fwd", "head_fwd", "conv_fwd", "convT_fwd", "skip_fwd"}
+    assert not forward & set(KC.BACKWARD_FAMILIES)
+    src = open(os.path.join(REPO, "thyroid-nodule-image-segmentation-unet-ddti_amd", "csrc", "runtime.hip")).read()
+    fwd_src, bwd_src = src[src.index("int forward_impl("):src.index("int backward_impl(")], src[src.index("int backward_impl("):]
+    for f in KC.BACKWARD_FAMILIES:
+        assert f'"{f}"' in bwd_src and f'"{f}"' not in fwd_src, f
