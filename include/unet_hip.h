@@ -39,6 +39,10 @@
  *                                                           the dihedral views of a batch, view-major
  *   unet_tta_merge / _host          (new)                  un-warp the per-view logits, average
  *                                                           them, threshold; per-pixel view votes
+ *   unet_curve_edges / _hist /      (new)                  threshold sweep: the class-split histogram
+ *   _stats / _host                                          of the logits and, per plane, Dice at every
+ *                                                           operating point, the best one and the
+ *                                                           AUROC numerator (ROC / PR curves)
  *   unet_adamw                      utils/trainer.py:41,92 AdamW.step (torch optim/adam.py
  *                                                           _single_tensor_adam, decoupled wd)
  *   unet_mask_counts                utils/trainer.py:217,236-242  sigmoid(x)>0.5 masks and
@@ -389,6 +393,48 @@ int unet_tta_merge(unet_ctx* ctx, const float* logits, int N, int C, int H, int 
                    int mode, float* score, uint8_t* mask, uint8_t* votes, unet_stream_t stream);
 int unet_tta_merge_host(const float* logits, int N, int C, int H, int W, uint32_t views, int mode,
                         float* score, uint8_t* mask, uint8_t* votes);
+
+/* Threshold sweep (csrc/curve.h; kernels in csrc/kernels_curve.hip): ROC / PR curves, Dice at every
+ * operating point and the choice of one, from a histogram of the logits split by target class.
+ * Everything is defined on the logits by float comparisons and integer sums (no transcendental on
+ * the device), so the device, the host twins and a NumPy restatement agree bit for bit.
+ *   Edges   B bins, B a power of two in 2..1024, separated by B - 1 strictly increasing float32
+ *           edges e[0..B-2].  unet_curve_edges (a HOST function) writes the standard ones, the
+ *           logits of the probabilities (j + 1) / B: e[j] = (float)log(t / (1 - t)), t = (j + 1) / B
+ *           in double, exactly antisymmetric, e[B/2 - 1] == 0.0f.
+ *   Bin     bin(x) = the number of j with e[j] < x, in 0..B-1: NaN and -inf in bin 0, +inf in bin
+ *           B-1, -0.0f not > 0.0f.  The search yields an in-range bin for any contents of `edges`.
+ *   Class   u = (uint8_t)(int)t, unet_mask_counts' target readout: u == 1 positive, u == 0 negative,
+ *           anything else ignored and counted.
+ *   Operating point k in 0..B: predicted positive iff bin(x) >= k (k = 0 every pixel, k = B none,
+ *           else x > e[k-1]).  k = B/2 is x > 0: unet_mask_counts' sigmoid(x) > 0.5 readout, except
+ *           for logits in (0, ~2^-24], where expf(-x) rounds to 1 and the readout says background.
+ *   unet_curve_hist   logits, targets: `planes` contiguous planes of hw floats ((N, C, H, W) is N C
+ *           planes).  plane_hist int32 [planes][2][B] (row 0 negatives, 1 positives) is overwritten;
+ *           total int64 [2 B + 1] is accumulated (+=, as unet_mask_counts' counts): the two rows
+ *           summed over the planes, then the ignored pixels.
+ *   unet_curve_stats  per plane, with P = sum pos, Nn = sum neg, TP_k / FP_k the sums over b >= k,
+ *           dice_k = (TP_k + FP_k + P == 0) ? 1.0 : (double)(2 TP_k) / (double)(TP_k + FP_k + P),
+ *           best_k the k of the largest dice_k (equal doubles: the smallest |k - B/2|, then the
+ *           smaller k) and auc2 = sum_b pos[b] (2 sum_{b' < b} neg[b'] + neg[b]) (AUROC = auc2 /
+ *           (2 P Nn)): out_i64 [planes][8] = {P, Nn, best_k, TP, FP, FN at best_k, auc2, 0};
+ *           dice_sum double [B + 1] += dice_k over the planes in ascending plane order (a fixed
+ *           order: two runs, and the device and the host twin, agree bit for bit).
+ * A null pointer, B no power of two or outside 2..1024, planes < 1 or hw < 1 is UNET_ERR_INVALID;
+ * hw >= 2^31 is UNET_ERR_SHAPE.  Pointers that are only 4-byte aligned and an hw that is no multiple
+ * of 4 are legal (a scalar path).  All work is enqueued on `stream` with no host synchronisation;
+ * the statistics use a context-owned scratch grown on demand.  The _host functions are the HOST
+ * twins (host pointers, the same curve.h rules). */
+int unet_curve_edges(int B, float* edges);
+int unet_curve_hist(unet_ctx* ctx, const float* logits, const float* targets, int planes, int64_t hw,
+                    const float* edges, int B, int32_t* plane_hist, int64_t* total,
+                    unet_stream_t stream);
+int unet_curve_hist_host(const float* logits, const float* targets, int planes, int64_t hw,
+                         const float* edges, int B, int32_t* plane_hist, int64_t* total);
+int unet_curve_stats(unet_ctx* ctx, const int32_t* plane_hist, int planes, int B, int64_t* out_i64,
+                     double* dice_sum, unet_stream_t stream);
+int unet_curve_stats_host(const int32_t* plane_hist, int planes, int B, int64_t* out_i64,
+                          double* dice_sum);
 
 /* Gradient buckets for data-parallel overlap.  Bucket b covers grads[offset, offset+len)
  * and is complete once the event recorded by unet_backward for it has fired; buckets

@@ -226,3 +226,13 @@ int k_tta_merge(const float* logits, int N, int C, int H, int W, uint32_t views,
 void tta_views_host(const float* x, int N, int C, int H, int W, uint32_t views, float* out);
 void tta_merge_host(const float* logits, int N, int C, int H, int W, uint32_t views, int mode, float* score,
                     uint8_t* mask, uint8_t* votes);
+
+// Threshold sweep (kernels_curve.hip; rules and the host twins in curve.h): the class-split
+// histogram of `planes` planes of hw logits (plane_hist overwritten, total accumulated) and the
+// per-plane statistics of such histograms (dice_sum accumulated in ascending plane order).
+// scratch holds curve_scratch_bytes(planes, B).  The callers have checked the arguments.
+size_t curve_scratch_bytes(int planes, int B);
+int k_curve_hist(const float* x, const float* t, int planes, int64_t hw, const float* edges, int B,
+                 int32_t* plane_hist, int64_t* total, hipStream_t s);
+int k_curve_stats(const int32_t* plane_hist, int planes, int B, void* scratch, int64_t* out_i64,
+                  double* dice_sum, hipStream_t s);

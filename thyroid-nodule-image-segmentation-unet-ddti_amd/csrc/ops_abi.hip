@@ -1,5 +1,5 @@
 // The stand-alone entry points of include/unet_hip.h: losses, distance transform, surface and
-// lesion metrics, connected components, test-time augmentation, resize and the training
+// lesion metrics, connected components, test-time augmentation, the threshold sweep, resize and the training
 // augmentations, each with its host twin where it has one.  None of them reads the layer graph
 // or a workspace plan (runtime.hip): they use the context's device, error string, launch timer
 // and their feature's scratch buffer (runtime_internal.h).
@@ -8,6 +8,7 @@
 #include "runtime_internal.h"
 #include "aug.h"
 #include "cc.h"
+#include "curve.h"
 #include "edt.h"
 #include "tta.h"
 #include "x3_split.h"
@@ -379,6 +380,70 @@ int unet_tta_merge_host(const float* logits, int N, int C, int H, int W, uint32_
         tta_merge_aliases(logits, N, C, H, W, views, score, mask, votes))
         return UNET_ERR_INVALID;
     return catch_to_status([&] { tta_merge_host(logits, N, C, H, W, views, mode, score, mask, votes); });
+}
+
+// ---- threshold sweep (kernels_curve.hip, curve.h) ----
+// UNET_OK, or the error code with *msg set
+static int curve_args_error(int planes, int64_t hw, int B, const char** msg) {
+    *msg = nullptr;
+    if (!curve_bins_ok(B)) *msg = "B must be a power of two in 2..1024";
+    else if (planes < 1) *msg = "planes >= 1";
+    else if (hw >= 0 && hw < 1) *msg = "hw >= 1";
+    if (*msg) return UNET_ERR_INVALID;
+    if (hw < 0) return UNET_OK;  // the statistics have no hw
+    if (hw >= (int64_t)1 << 31) *msg = "hw must be below 2^31";
+    return *msg ? UNET_ERR_SHAPE : UNET_OK;
+}
+
+int unet_curve_edges(int B, float* edges) {
+    if (!edges || !curve_bins_ok(B)) return UNET_ERR_INVALID;
+    curve_edges(B, edges);
+    return UNET_OK;
+}
+
+int unet_curve_hist(unet_ctx* c, const float* logits, const float* targets, int planes, int64_t hw,
+                    const float* edges, int B, int32_t* plane_hist, int64_t* total, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !logits || !targets || !edges || !plane_hist || !total) return UNET_ERR_INVALID;
+    const char* e;
+    if (int r = curve_args_error(planes, hw < 1 ? 0 : hw, B, &e)) return fail(c, r, "curve_hist: %s", e);
+    Launcher ln{c, (hipStream_t)stream};
+    return ln.run("curve/hist", 0,
+                  [&] { return k_curve_hist(logits, targets, planes, hw, edges, B, plane_hist, total, ln.s); });
+    ABI_CATCH(c)
+}
+
+int unet_curve_hist_host(const float* logits, const float* targets, int planes, int64_t hw, const float* edges,
+                         int B, int32_t* plane_hist, int64_t* total) {
+    if (!logits || !targets || !edges || !plane_hist || !total) return UNET_ERR_INVALID;
+    const char* e;
+    if (int r = curve_args_error(planes, hw < 1 ? 0 : hw, B, &e)) return r;
+    curve_hist_host(logits, targets, planes, hw, edges, B, plane_hist, total);
+    return UNET_OK;
+}
+
+int unet_curve_stats(unet_ctx* c, const int32_t* plane_hist, int planes, int B, int64_t* out_i64,
+                     double* dice_sum, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !plane_hist || !out_i64 || !dice_sum) return UNET_ERR_INVALID;
+    const char* e;
+    if (int r = curve_args_error(planes, -1, B, &e)) return fail(c, r, "curve_stats: %s", e);
+    if (int r = grow(c, c->curve, curve_scratch_bytes(planes, B), "curve")) return r;
+    Launcher ln{c, (hipStream_t)stream};
+    return ln.run("curve/stats", 0,
+                  [&] { return k_curve_stats(plane_hist, planes, B, c->curve.p, out_i64, dice_sum, ln.s); });
+    ABI_CATCH(c)
+}
+
+int unet_curve_stats_host(const int32_t* plane_hist, int planes, int B, int64_t* out_i64, double* dice_sum) {
+    if (!plane_hist || !out_i64 || !dice_sum) return UNET_ERR_INVALID;
+    const char* e;
+    if (int r = curve_args_error(planes, -1, B, &e)) return r;
+    return catch_to_status([&] {
+        std::vector<int32_t> cnt(2 * (size_t)(B + 1));
+        std::vector<double> dice((size_t)B + 1);
+        curve_stats_host(plane_hist, planes, B, out_i64, dice_sum, cnt.data(), cnt.data() + B + 1, dice.data());
+    });
 }
 
 int unet_x3_split_host(const float* v, int64_t n, uint16_t* out) {

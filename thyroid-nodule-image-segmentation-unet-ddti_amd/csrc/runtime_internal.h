@@ -242,6 +242,7 @@ struct unet_ctx {
     Scratch elastic;   // unet_elastic_u8: the row pass of both fields
     Scratch surface;   // unet_surface_stats: border planes, squared distances, gather partials
     Scratch cc;        // unet_components / _postprocess / _lesion_stats: labels, areas and flags, counts
+    Scratch curve;     // unet_curve_stats: the planes' dice_k before their ordered sum
     std::vector<void*> retired;
 
     int nconv() const { return (int)conv.size(); }

@@ -7,6 +7,8 @@ arithmetic of ModUNet / ResUNet; ``--use_amp_autocast`` stays parsed and ignored
 add connected-component post-processing and lesion-level detection to the test report;
 ``--tta {none,hflip,flips,d4}`` / ``--tta_merge {prob,logit}`` add flip / rotation test-time
 augmentation to it (a ``TTA`` block after the unchanged raw one);
+``--curve_metrics`` / ``--curve_bins`` add a threshold sweep (AUROC, AP, best Dice and its threshold)
+and ``--threshold`` the metrics at another operating point (an ``OPT`` block);
 ``--model_type`` picks the network
 (``ResUNet``: models/mod.py:88-131, what the reference hard-codes at main.py:120-122;
 ``ModUNet``: models/mod.py:9-66; ``UNet``: models/model.py, the BASELINE network and the
@@ -46,6 +48,17 @@ from utils.utils import Config, create_logger, set_seed  # noqa: E402
 def _flag(v):
     # the reference uses type=bool (main.py:59-60), which turns any string into True
     return bool(v)
+
+
+def _threshold(v):
+    from unet_hip.functional import THRESHOLD_CRITERIA, parse_threshold
+    if v in THRESHOLD_CRITERIA:
+        return v
+    try:
+        parse_threshold(float(v))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return float(v)
 
 
 def get_parser(argv=None):
@@ -112,6 +125,15 @@ def get_parser(argv=None):
                         "the merged masks, and --surface_metrics / --pp_* / --lesion_metrics read them")
     p.add_argument("--tta_merge", default="prob", choices=("prob", "logit"),
                    help="--tta: average the views' probabilities (prob) or their logits (logit)")
+    p.add_argument("--curve_metrics", action="store_true",
+                   help="test: also sweep the threshold on the GPU and report AUROC, average precision, "
+                        "the best global and mean per-image Dice with their thresholds")
+    p.add_argument("--curve_bins", type=int, default=256, metavar="B",
+                   help="operating points of the sweep: thresholds k / B (a power of two in 2..1024)")
+    p.add_argument("--threshold", type=_threshold, default=0.5, metavar="T",
+                   help="test: also report the metrics at another threshold: a probability in (0, 1) "
+                        "(snapped to k / B), or val-dice / val-image-dice to let the validation split "
+                        "pick the threshold of the best global / mean per-image Dice (not with --tta)")
     return p.parse_args(argv)
 
 

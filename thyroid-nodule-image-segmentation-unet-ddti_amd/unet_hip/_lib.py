@@ -123,6 +123,13 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "unet_tta_merge_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_uint32, c_int,
                                     c_void_p, c_void_p, c_void_p]),
+    "unet_curve_edges": (c_int, [c_int, c_void_p]),
+    "unet_curve_hist": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p,
+                                c_void_p, c_void_p]),
+    "unet_curve_hist_host": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p,
+                                     c_void_p]),
+    "unet_curve_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "unet_curve_stats_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "unet_num_buckets": (c_int, [c_void_p, P(c_int)]),
     "unet_bucket_range": (c_int, [c_void_p, c_int, P(c_int64), P(c_int64)]),
     "unet_stream_wait_bucket": (c_int, [c_void_p, c_int, c_void_p]),

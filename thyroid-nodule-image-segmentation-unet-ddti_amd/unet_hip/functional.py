@@ -446,3 +446,199 @@ def tta_predict(model, images, views="d4", mode="prob"):
     out = tta_merge(logits, N, m, mode)
     out["logits"] = logits
     return out
+
+
+# ---------------------------------------------------------------- threshold sweep
+CURVE_FIELDS = ("P", "Nn", "best_k", "TP", "FP", "FN", "auc2")
+THRESHOLD_CRITERIA = ("val-dice", "val-image-dice")
+
+
+def _curve_bins(bins):
+    bins = int(bins)
+    if not 2 <= bins <= 1024 or bins & (bins - 1):
+        raise ValueError(f"bins must be a power of two in 2..1024, got {bins}")
+    return bins
+
+
+def curve_edges(bins=256):
+    """The standard edges of the threshold sweep: a float32 CPU tensor of bins - 1 strictly increasing
+    logits, e[j] = logit((j + 1) / bins), exactly antisymmetric with e[bins / 2 - 1] == 0
+    (unet_curve_edges, a host function).  bins: a power of two in 2..1024."""
+    e = torch.empty(_curve_bins(bins) - 1, dtype=torch.float32)
+    _cc_host_call("unet_curve_edges", int(bins), e)
+    return e
+
+
+def _curve_planes(x, what):
+    """x as a contiguous float32 (planes, hw) view: (planes, hw) as it is, (..., H, W) with every
+    leading dimension a plane.  A float32 contiguous view is passed as it is (a 4-byte aligned base
+    is legal)."""
+    x = x.detach()
+    if x.dim() < 2:
+        raise ValueError(f"{what} must be (planes, hw) or (..., H, W), got {tuple(x.shape)}")
+    if not (x.dtype == torch.float32 and x.is_contiguous()):
+        x = x.float().contiguous()
+    hw = x.shape[-1] if x.dim() == 2 else x.shape[-1] * x.shape[-2]
+    return x.reshape(-1, hw) if hw else x.reshape(0, 0)
+
+
+def _curve_hist_args(logits, targets, edges, total):
+    if targets.shape != logits.shape:
+        raise ValueError(f"targets {tuple(targets.shape)} != logits {tuple(logits.shape)}")
+    x, t = _curve_planes(logits, "logits"), _curve_planes(targets, "targets")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"logits hold no pixel: {tuple(logits.shape)}")
+    edges = edges.detach().to(device=x.device, dtype=torch.float32).contiguous()
+    B = _curve_bins(edges.numel() + 1)
+    if total is None:
+        total = torch.zeros(2 * B + 1, dtype=torch.int64, device=x.device)
+    elif total.dtype != torch.int64 or total.numel() != 2 * B + 1 or total.device != x.device \
+            or not total.is_contiguous():
+        raise ValueError(f"total must be a contiguous int64 tensor of {2 * B + 1} on {x.device}")
+    return x, t, edges, B, total
+
+
+def curve_hist(logits, targets, edges, total=None):
+    """The class-split histogram of the logits on the device and the current stream (no host
+    synchronisation).  logits, targets: (planes, hw) or (..., H, W), every leading dimension a
+    plane.  With B = len(edges) + 1, a pixel's bin is the number of edges below its logit and its
+    class the integer cast of its target (1 positive, 0 negative, anything else ignored).  Returns
+    (plane_hist int32 (planes, 2, B), row 0 the negatives and row 1 the positives; total int64
+    (2 B + 1): the two rows summed over the planes, then the ignored pixels).  A given ``total`` is
+    accumulated into (and returned)."""
+    rt = _boundary_runtime(logits, "curve_hist")
+    x, t, edges, _, total = _curve_hist_args(logits, targets, edges, total)
+    return rt.curve_hist(x, t, edges, total), total
+
+
+def curve_hist_host(logits, targets, edges, total=None):
+    """``curve_hist`` of CPU tensors through the library's host twin."""
+    _cc_cpu(logits, "curve_hist_host")
+    _cc_cpu(targets, "curve_hist_host")
+    x, t, edges, B, total = _curve_hist_args(logits, targets, edges, total)
+    ph = torch.empty((x.shape[0], 2, B), dtype=torch.int32)
+    _cc_host_call("unet_curve_hist_host", x, t, x.shape[0], x.shape[1], edges, B, ph, total)
+    return ph, total
+
+
+def _curve_stats_args(plane_hist, dice_sum):
+    if plane_hist.dim() != 3 or plane_hist.shape[1] != 2 or plane_hist.dtype != torch.int32 or plane_hist.shape[0] < 1:
+        raise ValueError(f"plane_hist must be int32 (planes, 2, B), got {plane_hist.dtype} {tuple(plane_hist.shape)}")
+    B = _curve_bins(plane_hist.shape[2])
+    plane_hist = plane_hist.contiguous()
+    if dice_sum is None:
+        dice_sum = torch.zeros(B + 1, dtype=torch.float64, device=plane_hist.device)
+    elif dice_sum.dtype != torch.float64 or dice_sum.numel() != B + 1 or dice_sum.device != plane_hist.device \
+            or not dice_sum.is_contiguous():
+        raise ValueError(f"dice_sum must be a contiguous float64 tensor of {B + 1} on {plane_hist.device}")
+    return plane_hist, dice_sum
+
+
+def _curve_stats_dict(out, dice_sum):
+    d = {k: out[:, i] for i, k in enumerate(CURVE_FIELDS)}
+    d["dice_sum"] = dice_sum
+    return d
+
+
+def curve_stats(plane_hist, dice_sum=None):
+    """The per-plane statistics of ``curve_hist``'s plane_hist on the device: a dict of int64
+    (planes,) tensors ``P``, ``Nn`` (positives, negatives), ``best_k`` (the operating point of the
+    plane's largest Dice; ties: nearest to B / 2, then the smaller), ``TP``, ``FP``, ``FN`` there and
+    ``auc2`` (AUROC = auc2 / (2 P Nn)), plus ``dice_sum`` float64 (B + 1): the planes' Dice at every
+    operating point k = 0..B, added in ascending plane order to a given ``dice_sum``."""
+    rt = _boundary_runtime(plane_hist, "curve_stats")
+    plane_hist, dice_sum = _curve_stats_args(plane_hist, dice_sum)
+    return _curve_stats_dict(rt.curve_stats(plane_hist, dice_sum), dice_sum)
+
+
+def curve_stats_host(plane_hist, dice_sum=None):
+    """``curve_stats`` of a CPU tensor through the library's host twin."""
+    _cc_cpu(plane_hist, "curve_stats_host")
+    plane_hist, dice_sum = _curve_stats_args(plane_hist, dice_sum)
+    planes, _, B = plane_hist.shape
+    out = torch.empty((planes, 8), dtype=torch.int64)
+    _cc_host_call("unet_curve_stats_host", plane_hist, planes, B, out, dice_sum)
+    return _curve_stats_dict(out, dice_sum)
+
+
+def curve_best(values):
+    """The operating point of the largest of the B + 1 values; ties: the k nearest to B / 2, then the
+    smaller k (curve.h's curve_better)."""
+    B = len(values) - 1
+    return min(range(B + 1), key=lambda k: (-values[k], abs(k - B // 2), k))
+
+
+def curve_summary(total, dice_sum, n_planes, edges):
+    """Read the curves off what one transfer brings back: ``total`` (2 B + 1 Python ints: the
+    negatives' and the positives' histogram, the ignored pixels), ``dice_sum`` (B + 1 floats) over
+    ``n_planes`` planes, and the B - 1 ``edges``.  Pure Python.  Operating point k in 0..B predicts a
+    pixel positive iff its bin is >= k and is reported as the probability k / B.  Returns a dict:
+    ``auroc`` (exact from the global histogram, ties counted half; NaN without both classes), ``ap``
+    (sum over k ascending of (R_k - R_{k+1}) Prec_k, Prec = 1 where nothing is predicted; NaN without
+    positives), ``dice_global`` (B + 1 values) with ``best_global_k`` / ``_threshold`` / ``_dice``,
+    ``dice_image`` = dice_sum / n_planes with ``best_image_k`` / ``_threshold`` / ``_dice``, both at
+    k = B / 2 (``dice_global_half``, ``dice_image_half``), and ``bins``, ``positives``, ``negatives``,
+    ``ignored``, ``planes``."""
+    total = [int(v) for v in total]
+    dice_sum = [float(v) for v in dice_sum]
+    B = _curve_bins(len(edges) + 1)
+    if len(total) != 2 * B + 1 or len(dice_sum) != B + 1:
+        raise ValueError(f"{B} bins need {2 * B + 1} totals and {B + 1} Dice sums, got {len(total)} and {len(dice_sum)}")
+    neg, pos, ignored = total[:B], total[B:2 * B], total[2 * B]
+    P, Nn = sum(pos), sum(neg)
+    tp, fp = [0] * (B + 1), [0] * (B + 1)
+    for b in range(B - 1, -1, -1):
+        tp[b], fp[b] = tp[b + 1] + pos[b], fp[b + 1] + neg[b]
+    below = auc2 = 0
+    for b in range(B):
+        auc2 += pos[b] * (2 * below + neg[b])
+        below += neg[b]
+    nan = float("nan")
+    auroc = auc2 / (2 * P * Nn) if P and Nn else nan
+    if P:
+        prec = [tp[k] / (tp[k] + fp[k]) if tp[k] + fp[k] else 1.0 for k in range(B + 1)]
+        ap = sum((tp[k] - tp[k + 1]) / P * prec[k] for k in range(B))
+    else:
+        ap = nan
+    dice_global = [2 * tp[k] / (tp[k] + fp[k] + P) if tp[k] + fp[k] + P else 1.0 for k in range(B + 1)]
+    n = int(n_planes)
+    dice_image = [v / n if n else nan for v in dice_sum]
+    gk = curve_best(dice_global)
+    ik = curve_best(dice_image) if n else B // 2
+    return dict(bins=B, planes=n, positives=P, negatives=Nn, ignored=ignored, auroc=auroc, ap=ap,
+                dice_global=dice_global, best_global_k=gk, best_global_threshold=gk / B,
+                best_global_dice=dice_global[gk], dice_global_half=dice_global[B // 2],
+                dice_image=dice_image, best_image_k=ik, best_image_threshold=ik / B,
+                best_image_dice=dice_image[ik], dice_image_half=dice_image[B // 2])
+
+
+def parse_threshold(value, bins=256):
+    """``config.threshold`` -> (criterion or None, k or None).  0.5 (the default) is (None, None):
+    the plain readout.  A float in (0, 1) is snapped to the nearest operating point k / bins with
+    1 <= k <= bins - 1; "val-dice" / "val-image-dice" name the criterion the validation split
+    decides k by."""
+    if value is None:
+        return None, None
+    if isinstance(value, str) and value in THRESHOLD_CRITERIA:
+        return value, None
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not 0.0 < v < 1.0:
+        raise ValueError(f"threshold must be a float in (0, 1) or one of {THRESHOLD_CRITERIA}, got {value!r}")
+    if v == 0.5:
+        return None, None
+    B = _curve_bins(bins)
+    return None, min(max(int(v * B + 0.5), 1), B - 1)
+
+
+def curve_predict(logits, k, edges):
+    """The bool mask of operating point k in 0..B: bin(logits) >= k, i.e. logits > edges[k - 1] for
+    1 <= k <= B - 1, everything for k = 0 and nothing for k = B."""
+    B = edges.numel() + 1
+    if k <= 0:
+        return torch.ones_like(logits, dtype=torch.bool)
+    if k >= B:
+        return torch.zeros_like(logits, dtype=torch.bool)
+    return logits > edges[k - 1]

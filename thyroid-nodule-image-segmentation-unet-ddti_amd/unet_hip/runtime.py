@@ -277,6 +277,27 @@ class UNetRuntime:
         _lib.check(rc, self.ctx, "unet_tta_merge")
         return score, mask, votes
 
+    def curve_hist(self, logits, targets, edges, total):
+        """plane_hist int32 (planes, 2, B) of logits / targets (planes, hw) against the B - 1 device
+        edges; total int64 (2 B + 1) is accumulated (unet_curve_hist)."""
+        planes, hw = logits.shape
+        B = edges.numel() + 1
+        ph = torch.empty((planes, 2, B), dtype=torch.int32, device=logits.device)
+        rc = self.lib.unet_curve_hist(self.ctx, _lib.ptr(logits), _lib.ptr(targets), planes, hw, _lib.ptr(edges),
+                                      B, _lib.ptr(ph), _lib.ptr(total), _lib.stream_ptr(logits.device))
+        _lib.check(rc, self.ctx, "unet_curve_hist")
+        return ph
+
+    def curve_stats(self, plane_hist, dice_sum):
+        """int64 (planes, 8) {P, Nn, best_k, TP, FP, FN, auc2, 0} of plane_hist (planes, 2, B);
+        dice_sum float64 (B + 1) is accumulated in ascending plane order (unet_curve_stats)."""
+        planes, _, B = plane_hist.shape
+        out = torch.empty((planes, 8), dtype=torch.int64, device=plane_hist.device)
+        rc = self.lib.unet_curve_stats(self.ctx, _lib.ptr(plane_hist), planes, B, _lib.ptr(out),
+                                       _lib.ptr(dice_sum), _lib.stream_ptr(plane_hist.device))
+        _lib.check(rc, self.ctx, "unet_curve_stats")
+        return out
+
     def stream_wait_bucket(self, b, stream):
         rc = self.lib.unet_stream_wait_bucket(self.ctx, b, ctypes.c_void_p(stream.cuda_stream))
         _lib.check(rc, self.ctx, "unet_stream_wait_bucket")

@@ -39,6 +39,14 @@ What runs where (MI355X-first):
   still that of the plain forward (the first view); a ``TTA_*`` block reports the merged mask and
   the share of pixels the views disagree on, and the surface, ``PP_*`` and lesion blocks and the
   contour PNGs then read the merged mask.
+* ``test()`` with ``config.curve_metrics`` (``config.curve_bins``, default 256): a threshold sweep on
+  the device (``unet_hip.curve_hist`` / ``curve_stats``: one class-split histogram of the plain
+  forward's channel-0 logits per batch); 2 B + 1 integers and B + 1 doubles come back once and a
+  ``Curve Metrics`` block reports AUROC, average precision, the best global and the best mean
+  per-image Dice with their thresholds, and the mean per-image Dice at 0.5.  ``config.threshold``
+  (a float in (0, 1), snapped to k / B, or ``"val-dice"`` / ``"val-image-dice"``: the same sweep over
+  the validation split decides) adds an ``OPT_*`` block of the confusion metrics at that threshold;
+  every other block keeps reading the 0.5 mask.
 """
 import os
 import random
@@ -341,6 +349,22 @@ class Trainer:
             tcounts = torch.zeros(6, dtype=torch.int64, device=self.device)
             tdis = torch.zeros(1, dtype=torch.int64, device=self.device)
         src = " (TTA mask)" if tta_on else ""
+        curve_on = bool(getattr(cfg, "curve_metrics", False))
+        bins = int(getattr(cfg, "curve_bins", None) or 256)
+        criterion, opt_k = unet_hip.functional.parse_threshold(getattr(cfg, "threshold", None), bins)
+        opt_on = criterion is not None or opt_k is not None
+        if opt_on and tta_on:
+            raise ValueError(f"threshold={cfg.threshold!r} with tta={tta!r}: merging the views at a threshold "
+                             "other than 0.5 is not supported; use one of the two")
+        if curve_on or opt_on:
+            edges = unet_hip.curve_edges(bins).to(self.device)
+        if criterion is not None:  # the validation split decides the operating point
+            vs = self._curve_summary(self._curve_sweep(self.val_loader, edges, "Threshold sweep (val)"), edges)
+            opt_k = vs["best_global_k" if criterion == "val-dice" else "best_image_k"]
+        if opt_on:
+            ocounts = torch.zeros(6, dtype=torch.int64, device=self.device)
+        if curve_on:  # the histogram rows + ignored pixels, the Dice sums, the planes
+            cacc = self._curve_acc(bins)
         for batch in tqdm(self.test_loader, desc="Testing Model", leave=True):
             if batch is None:  # empty DataParallel shard: nothing to count on this rank
                 keep.append(None)
@@ -355,6 +379,7 @@ class Trainer:
                 logits = self.model(images)
             mask = torch.empty(logits.shape, dtype=torch.uint8, device=self.device)
             self.rt.mask_counts(logits, masks, counts, mask)
+            raw = logits
             if tta_on:
                 # the merged mask as +-1 logits, so that every kernel downstream reads the mask
                 # the merge formed (in "prob" mode the score is a probability, not a logit)
@@ -362,6 +387,11 @@ class Trainer:
                 logits = mask.float() * 2 - 1
                 self.rt.mask_counts(logits, masks, tcounts)
                 tdis += ((merged["votes"] > 0) & (merged["votes"] < n_views)).sum()
+            if curve_on:  # (no TTA with a threshold; under TTA `raw` is the first view's logits)
+                self._curve_add(cacc, raw, masks, edges)
+            if opt_on:  # the mask of operating point opt_k as +-1 logits for the same readout
+                om = unet_hip.functional.curve_predict(raw[:, :1], opt_k, edges)
+                self.rt.mask_counts(om.float() * 2 - 1, masks[:, :1].contiguous(), ocounts)
             if surface:
                 ssums += self._surface_sums(logits, masks)
             if post:
@@ -454,6 +484,34 @@ class Trainer:
             self.logger.info(lmsg)
             m.update(LesionRecall=rec, LesionPrecision=prec, FPComponentsPerImage=fpc,
                      PredComponents=n_pred, GTComponents=n_gt)
+        if curve_on:
+            cs = self._curve_summary(cacc, edges)  # the one transfer
+            cmsg = (f"Curve Metrics ({bins} bins) — AUROC={cs['auroc']:.4f}, AP={cs['ap']:.4f}\n"
+                    f"  Best global Dice={cs['best_global_dice']:.4f} at threshold {cs['best_global_threshold']:.4f} "
+                    f"(Dice at 0.5: {cs['dice_global_half']:.4f})\n"
+                    f"  Best mean per-image Dice={cs['best_image_dice']:.4f} at threshold "
+                    f"{cs['best_image_threshold']:.4f} (at 0.5: {cs['dice_image_half']:.4f}) over {cs['planes']} images\n"
+                    f"  Ignored pixels={cs['ignored']}")
+            if self.rank0:
+                print(cmsg)
+            self.logger.info(cmsg)
+            m.update(Curve_AUROC=cs["auroc"], Curve_AP=cs["ap"], Curve_BestDice=cs["best_global_dice"],
+                     Curve_BestDiceThreshold=cs["best_global_threshold"], Curve_Dice=cs["dice_global_half"],
+                     Curve_BestImageDice=cs["best_image_dice"],
+                     Curve_BestImageDiceThreshold=cs["best_image_threshold"],
+                     Curve_ImageDice=cs["dice_image_half"], Curve_Ignored=cs["ignored"], Curve_Bins=bins)
+        if opt_on:
+            om = global_metrics_from_counts(self._reduce_counts(ocounts).tolist())
+            how = f"chosen by {criterion}" if criterion else f"snapped from {float(cfg.threshold):g}"
+            omsg = (f"Operating point — threshold {opt_k / bins:.6f} (k={opt_k} of {bins}, {how})\n"
+                    f"  TP={om['TP']}, FP={om['FP']}, FN={om['FN']}, TN={om['TN']}\n"
+                    f"  ACC={om['ACC']:.4f}, Precision={om['Precision']:.4f}, "
+                    f"Recall={om['Recall']:.4f}, F1={om['F1']:.4f}, IoU={om['IoU']:.4f}")
+            if self.rank0:
+                print(omsg)
+            self.logger.info(omsg)
+            m.update({"OPT_" + k: v for k, v in om.items()})
+            m["OPT_Threshold"] = opt_k / bins
         if _distributed() and self._can_plot():
             # one set of PNGs over the whole test set, in the reference's sample order: batch
             # by batch, each batch's shards in rank order (DataParallel's gather order)
@@ -466,6 +524,40 @@ class Trainer:
         if keep and self.rank0:
             self._plot_contours(keep)
         return m
+
+    # ---- threshold sweep: device-side accumulators, read once ----
+    def _curve_acc(self, bins):
+        return dict(total=torch.zeros(2 * bins + 1, dtype=torch.int64, device=self.device),
+                    dice=torch.zeros(bins + 1, dtype=torch.float64, device=self.device), planes=0)
+
+    @staticmethod
+    def _curve_add(acc, logits, masks, edges):
+        """One histogram and one statistics call on the batch's channel-0 planes."""
+        ph, _ = unet_hip.curve_hist(logits[:, :1], masks[:, :1], edges, acc["total"])
+        unet_hip.curve_stats(ph, acc["dice"])
+        acc["planes"] += logits.shape[0]
+
+    def _curve_sweep(self, loader, edges, desc):
+        """The sweep over a loader in eval mode (the caller has synchronised the BN buffers)."""
+        acc = self._curve_acc(edges.numel() + 1)
+        for batch in tqdm(loader, desc=desc, leave=True):
+            if batch is None:  # empty DataParallel shard
+                continue
+            images, masks = batch
+            logits = self.model(images.to(self.device).float())
+            self._curve_add(acc, logits, masks.to(self.device).float(), edges)
+        return acc
+
+    def _curve_summary(self, acc, edges):
+        """All-reduce the accumulators, bring them back in one transfer, read the curves."""
+        ints = torch.cat([acc["total"], torch.tensor([acc["planes"]], dtype=torch.int64, device=self.device)])
+        if _distributed():
+            dist.all_reduce(ints)
+            dist.all_reduce(acc["dice"])
+        back = torch.cat([ints, acc["dice"].view(torch.int64)]).cpu()  # the one transfer
+        n = ints.numel()
+        return unet_hip.curve_summary(back[:n - 1].tolist(), back[n:].view(torch.float64).tolist(),
+                                      int(back[n - 1]), edges)
 
     @staticmethod
     def _surface_sums(logits, masks):
