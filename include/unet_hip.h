@@ -555,6 +555,47 @@ int unet_clahe_u8(unet_ctx* ctx, const uint8_t* src, int h, int w, uint8_t* dst,
 int unet_clahe_u8_host(const uint8_t* src, int h, int w, uint8_t* dst, double clip, int gx,
                        int gy);
 
+/* Predict-mode export (csrc/export.h holds the rules; no reference counterpart beyond the contour
+ * plot of utils/trainer.py:262-299, which this replaces without matplotlib or scikit-image).
+ *
+ * unet_resize_f32_plan (host only): Pillow's BILINEAR plan of one axis in_size -> out_size for
+ * mode "F" images: coeffs [out_size][*ksize] doubles and bounds [out_size] {first, count}, the
+ * layout of unet_resize_plan.  coeffs / bounds NULL: *ksize alone.
+ *
+ * unet_resize_f32_mask: plane (oh, ow) <- the float32 plane src (h, w) resized as
+ * Image.fromarray(src, "F").resize((ow, oh), BILINEAR) does, bit for bit (double accumulation of
+ * float pixel x double tap, product and sum rounded separately; the horizontal pass first into a
+ * float32 intermediate; an unchanged axis skipped), and mask (oh, ow) uint8 in {0, 1} <- its
+ * threshold: kind UNET_EXPORT_SIGMOID_HALF: sigmoid(v) > 0.5f as unet_mask_counts reads it (thr
+ * ignored); UNET_EXPORT_GREATER: v > thr.  plane may be NULL (the resized plane then never reaches
+ * memory beyond the intermediate).  kh / bh / ksh: the plan w -> ow, kv / bv / ksv: h -> oh (device
+ * memory; an unchanged axis needs none).  The intermediate lives in a context-owned scratch grown
+ * on demand without a host synchronisation (the outgrown buffer is kept until unet_destroy): issue
+ * a context's calls on one stream, or order the streams.  A non-positive size or an unknown kind
+ * is UNET_ERR_INVALID.
+ *
+ * unet_overlay_u8: rgb (h, w, 3) interleaved bytes <- the gray plane (h, w) with the prediction
+ * mask pred (h, w; nonzero = foreground) tinted at alpha in 0..256 (0: none) inside and its contour
+ * of width r in 1..3 (foreground pixels with a background or outside pixel at city-block distance
+ * <= r) solid red on top of the solid blue contour of gt (h, w), which may be NULL.  stats:
+ * int64[6] = {area, contour pixels, x0, y0, x1, y1} of pred (inclusive box; an empty mask gives
+ * 0, 0, -1, -1, -1, -1), overwritten.  r or alpha outside its range, or a non-positive size, is
+ * UNET_ERR_INVALID.  The _host functions are the HOST twins (host pointers, same source). */
+enum { UNET_EXPORT_SIGMOID_HALF = 0, UNET_EXPORT_GREATER = 1 };
+int unet_resize_f32_plan(int in_size, int out_size, double* coeffs, int32_t* bounds, int* ksize);
+int unet_resize_f32_mask(unet_ctx* ctx, const float* src, int h, int w, int oh, int ow,
+                         const double* kh, const int32_t* bh, int ksh, const double* kv,
+                         const int32_t* bv, int ksv, int kind, float thr, float* plane,
+                         uint8_t* mask, unet_stream_t stream);
+int unet_resize_f32_mask_host(const float* src, int h, int w, int oh, int ow, const double* kh,
+                              const int32_t* bh, int ksh, const double* kv, const int32_t* bv,
+                              int ksv, int kind, float thr, float* plane, uint8_t* mask);
+int unet_overlay_u8(unet_ctx* ctx, const uint8_t* gray, const uint8_t* pred, const uint8_t* gt,
+                    int h, int w, int r, int alpha, uint8_t* rgb, int64_t* stats,
+                    unet_stream_t stream);
+int unet_overlay_u8_host(const uint8_t* gray, const uint8_t* pred, const uint8_t* gt, int h, int w,
+                         int r, int alpha, uint8_t* rgb, int64_t* stats);
+
 /* Kernel-schedule options of a context (new; no reference counterpart).  The defaults are
  * the measured-best schedules; the named alternatives (tiles, LDS-DMA vs register-staged
  * bf16 kernels, XCD block order, ...) exist for A/B runs and the bit-identity tests.  The

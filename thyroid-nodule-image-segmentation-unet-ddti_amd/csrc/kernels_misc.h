@@ -236,3 +236,14 @@ int k_curve_hist(const float* x, const float* t, int planes, int64_t hw, const f
                  int32_t* plane_hist, int64_t* total, hipStream_t s);
 int k_curve_stats(const int32_t* plane_hist, int planes, int B, void* scratch, int64_t* out_i64,
                   double* dice_sum, hipStream_t s);
+
+// Predict-mode export (kernels_export.hip; rules and the host twins in export.h): the float32
+// resize of one plane fused with the threshold (plane may be null; scratch holds
+// export_scratch_bytes(h, w, ow)) and the contour / tint overlay with the mask statistics (gt may
+// be null; stats: 6 int64, overwritten).  The callers have checked the arguments.
+size_t export_scratch_bytes(int h, int w, int ow);
+int k_resize_f32_mask(const float* src, int h, int w, int oh, int ow, const double* kh, const int* bh,
+                      int ksh, const double* kv, const int* bv, int ksv, int kind, float thr, void* scratch,
+                      float* plane, uint8_t* mask, hipStream_t s);
+int k_overlay_u8(const uint8_t* gray, const uint8_t* pred, const uint8_t* gt, int h, int w, int r, int alpha,
+                 uint8_t* rgb, int64_t* stats, hipStream_t s);

@@ -1,6 +1,7 @@
 // The stand-alone entry points of include/unet_hip.h: losses, distance transform, surface and
-// lesion metrics, connected components, test-time augmentation, the threshold sweep, resize and the training
-// augmentations, each with its host twin where it has one.  None of them reads the layer graph
+// lesion metrics, connected components, test-time augmentation, the threshold sweep, the predict-mode
+// export (resize back + overlay), resize and the training augmentations, each with its host twin where
+// it has one.  None of them reads the layer graph
 // or a workspace plan (runtime.hip): they use the context's device, error string, launch timer
 // and their feature's scratch buffer (runtime_internal.h).
 #include <algorithm>
@@ -10,6 +11,7 @@
 #include "cc.h"
 #include "curve.h"
 #include "edt.h"
+#include "export.h"
 #include "tta.h"
 #include "x3_split.h"
 
@@ -444,6 +446,82 @@ int unet_curve_stats_host(const int32_t* plane_hist, int planes, int B, int64_t*
         std::vector<double> dice((size_t)B + 1);
         curve_stats_host(plane_hist, planes, B, out_i64, dice_sum, cnt.data(), cnt.data() + B + 1, dice.data());
     });
+}
+
+// ---- predict-mode export (kernels_export.hip, export.h) ----
+// null, or what is wrong with the arguments of the resize
+static const char* export_resize_error(const float* src, int h, int w, int oh, int ow, const double* kh,
+                                       const int32_t* bh, int ksh, const double* kv, const int32_t* bv, int ksv,
+                                       int kind, const uint8_t* mask) {
+    if (!src || !mask) return "src and mask must not be null";
+    if (h < 1 || w < 1 || oh < 1 || ow < 1) return "h, w, oh, ow >= 1";
+    if (!export_kind_ok(kind)) return "kind must be 0 (sigmoid > 0.5) or 1 (greater than thr)";
+    if ((int64_t)h * ow >= (int64_t)1 << 31 || (int64_t)oh * ow >= (int64_t)1 << 31) return "plane too large";
+    if ((ow != w && (!kh || !bh || ksh < 1)) || (oh != h && (!kv || !bv || ksv < 1)))
+        return "missing coefficient tables";
+    return nullptr;
+}
+
+static const char* export_overlay_error(const uint8_t* gray, const uint8_t* pred, int h, int w, int r, int alpha,
+                                        const uint8_t* rgb, const int64_t* stats) {
+    if (!gray || !pred || !rgb || !stats) return "gray, pred, rgb and stats must not be null";
+    if (h < 1 || w < 1) return "h, w >= 1";
+    if ((int64_t)h * w >= (int64_t)1 << 29) return "plane too large";
+    if (!export_width_ok(r)) return "contour width r must be 1, 2 or 3";
+    if (!export_alpha_ok(alpha)) return "alpha must be in 0..256";
+    return nullptr;
+}
+
+int unet_resize_f32_plan(int in_size, int out_size, double* coeffs, int32_t* bounds, int* ksize) {
+    ABI_TRY
+    if (in_size < 1 || out_size < 1 || !ksize) return UNET_ERR_INVALID;
+    *ksize = export_resize_plan(in_size, out_size, coeffs, bounds);
+    return UNET_OK;
+    ABI_CATCH((unet_ctx*)nullptr)
+}
+
+int unet_resize_f32_mask(unet_ctx* c, const float* src, int h, int w, int oh, int ow, const double* kh,
+                         const int32_t* bh, int ksh, const double* kv, const int32_t* bv, int ksv, int kind,
+                         float thr, float* plane, uint8_t* mask, unet_stream_t stream) {
+    ABI_TRY
+    if (!c) return UNET_ERR_INVALID;
+    if (const char* e = export_resize_error(src, h, w, oh, ow, kh, bh, ksh, kv, bv, ksv, kind, mask))
+        return fail(c, UNET_ERR_INVALID, "resize_f32_mask: %s", e);
+    if (int r = grow(c, c->exportbuf, export_scratch_bytes(h, w, ow), "export")) return r;
+    Launcher ln{c, (hipStream_t)stream};
+    return ln.run("export/resize", 0, [&] {
+        return k_resize_f32_mask(src, h, w, oh, ow, kh, bh, ksh, kv, bv, ksv, kind, thr, c->exportbuf.p, plane, mask,
+                                 ln.s);
+    });
+    ABI_CATCH(c)
+}
+
+int unet_resize_f32_mask_host(const float* src, int h, int w, int oh, int ow, const double* kh, const int32_t* bh,
+                              int ksh, const double* kv, const int32_t* bv, int ksv, int kind, float thr,
+                              float* plane, uint8_t* mask) {
+    if (export_resize_error(src, h, w, oh, ow, kh, bh, ksh, kv, bv, ksv, kind, mask)) return UNET_ERR_INVALID;
+    return catch_to_status([&] {
+        std::vector<float> tmp(ow != w ? (size_t)h * ow : 0);
+        export_resize_mask_host(src, h, w, oh, ow, kh, bh, ksh, kv, bv, ksv, kind, thr, tmp.data(), plane, mask);
+    });
+}
+
+int unet_overlay_u8(unet_ctx* c, const uint8_t* gray, const uint8_t* pred, const uint8_t* gt, int h, int w, int r,
+                    int alpha, uint8_t* rgb, int64_t* stats, unet_stream_t stream) {
+    ABI_TRY
+    if (!c) return UNET_ERR_INVALID;
+    if (const char* e = export_overlay_error(gray, pred, h, w, r, alpha, rgb, stats))
+        return fail(c, UNET_ERR_INVALID, "overlay: %s", e);
+    Launcher ln{c, (hipStream_t)stream};
+    return ln.run("export/overlay", 0, [&] { return k_overlay_u8(gray, pred, gt, h, w, r, alpha, rgb, stats, ln.s); });
+    ABI_CATCH(c)
+}
+
+int unet_overlay_u8_host(const uint8_t* gray, const uint8_t* pred, const uint8_t* gt, int h, int w, int r, int alpha,
+                         uint8_t* rgb, int64_t* stats) {
+    if (export_overlay_error(gray, pred, h, w, r, alpha, rgb, stats)) return UNET_ERR_INVALID;
+    export_overlay_host(gray, pred, gt, h, w, r, alpha, rgb, stats);
+    return UNET_OK;
 }
 
 int unet_x3_split_host(const float* v, int64_t n, uint16_t* out) {

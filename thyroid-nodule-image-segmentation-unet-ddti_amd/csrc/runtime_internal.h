@@ -243,6 +243,7 @@ struct unet_ctx {
     Scratch surface;   // unet_surface_stats: border planes, squared distances, gather partials
     Scratch cc;        // unet_components / _postprocess / _lesion_stats: labels, areas and flags, counts
     Scratch curve;     // unet_curve_stats: the planes' dice_k before their ordered sum
+    Scratch exportbuf; // unet_resize_f32_mask: the float32 intermediate of the horizontal pass
     std::vector<void*> retired;
 
     int nconv() const { return (int)conv.size(); }

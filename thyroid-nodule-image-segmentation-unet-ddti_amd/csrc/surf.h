@@ -31,12 +31,10 @@
 
 #define SURF_HD EDT_HD
 
-// ---- the mask readout of unet_mask_counts (utils/trainer.py:217-220) ----
-// sigmoid(x) > 0.5 in float32, as torch forms it
-SURF_HD bool surf_pred(float x) { return 1.f / (1.f + expf(-x)) > 0.5f; }
-// numpy astype(uint8) truncation of the {0, 1} float targets; == 1 is foreground
-SURF_HD uint8_t surf_target_u8(float t) { return (uint8_t)(int)t; }
-SURF_HD bool surf_target(float t) { return surf_target_u8(t) == 1; }
+// ---- the mask readout of unet_mask_counts (utils/trainer.py:217-220): surf_pred, surf_target_u8,
+// surf_target, in mask_readout.h so that a host-only build shares the one definition ----
+#define READOUT_HD SURF_HD
+#include "mask_readout.h"
 
 // ---- border ----
 // fg(i, j): the mask inside the image

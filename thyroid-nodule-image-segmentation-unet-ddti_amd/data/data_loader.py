@@ -172,6 +172,12 @@ class DecodeU8:
         return self._plane(img), self._plane(mask)
 
 
+def decode_u8(pic):
+    """One PIL image as the (H, W) uint8 plane of the device pipeline (``DecodeU8`` for a frame
+    without a mask)."""
+    return DecodeU8._plane(pic)
+
+
 def u8_collate(batch):
     """Keep variable-size uint8 planes as lists (resized on the device); each plane keeps its
     ``resample`` tag and ``aug`` record."""

@@ -9,11 +9,16 @@ add connected-component post-processing and lesion-level detection to the test r
 augmentation to it (a ``TTA`` block after the unchanged raw one);
 ``--curve_metrics`` / ``--curve_bins`` add a threshold sweep (AUROC, AP, best Dice and its threshold)
 and ``--threshold`` the metrics at another operating point (an ``OPT`` block);
+``--mode predict --input_dir DIR --output_dir DIR`` segments frames that have no masks and writes
+source-size mask and contour-overlay PNGs and a ``predictions.csv`` (``--contour_width``,
+``--overlay_alpha``, ``--save_prob``), and ``--save_overlays`` writes the test split's overlays
+(``test_overlay_<index>.png``) without matplotlib: the device-side successor of the reference's
+contour plot (utils/trainer.py:262-299);
 ``--model_type`` picks the network
 (``ResUNet``: models/mod.py:88-131, what the reference hard-codes at main.py:120-122;
 ``ModUNet``: models/mod.py:9-66; ``UNet``: models/model.py, the BASELINE network and the
 default here; ``--base_filters`` / ``--depth`` for the mod.py ones, default 64 / 5 as
-there), ``--mode {train,test,both}`` replaces the commented-out
+there), ``--mode {train,test,both,predict}`` replaces the commented-out
 ``trainer.train()`` / hard-wired ``trainer.test()`` (:156-157), and ``--synthetic N`` runs
 on N synthetic samples per split when the DDTI images are not on disk.
 
@@ -36,7 +41,7 @@ if HERE not in sys.path:
 
 from data.data_loader import (DataParallelShardSampler, DecodeU8, DeviceResizeLoader,  # noqa: E402
                               MedicalDataset, SyntheticSegmentation, create_dataloader,
-                              dp_collate, u8_collate)
+                              decode_u8, dp_collate, u8_collate)
 from models.mod import ResUNet  # noqa: E402
 from models.mod import UNet as ModUNet  # noqa: E402
 from models.model import UNet  # noqa: E402
@@ -102,7 +107,19 @@ def get_parser(argv=None):
     p.add_argument("--mfma", default="fp32", choices=("fp32", "bf16"),
                    help="ModUNet / ResUNet: conv GEMM arithmetic (bf16: operands rounded to "
                         "bf16, f32 accumulate; base_filters 64, 128 or 256)")
-    p.add_argument("--mode", choices=["train", "test", "both"], default="test")
+    p.add_argument("--mode", choices=["train", "test", "both", "predict"], default="test")
+    p.add_argument("--input_dir", default="", type=str, help="predict: the directory of image files to segment")
+    p.add_argument("--output_dir", default="", type=str,
+                   help="predict: where <stem>_mask.png, <stem>_overlay.png and predictions.csv go")
+    p.add_argument("--contour_width", type=int, default=1, choices=(1, 2, 3),
+                   help="predict / --save_overlays: contour width in pixels")
+    p.add_argument("--overlay_alpha", type=int, default=0, metavar="A",
+                   help="predict / --save_overlays: red tint of the predicted region, 0..256 (0: none)")
+    p.add_argument("--save_prob", action="store_true",
+                   help="predict: also write <stem>_score.npy, the score plane at the source size")
+    p.add_argument("--save_overlays", action="store_true",
+                   help="test: write test_overlay_<index>.png (prediction red, ground truth blue) for every "
+                        "test sample, rendered on the GPU; needs neither matplotlib nor scikit-image")
     p.add_argument("--image_size", type=int, default=512)
     p.add_argument("--synthetic", type=int, default=0, help="synthetic samples per split")
     p.add_argument("--surface_metrics", action="store_true",
@@ -134,11 +151,101 @@ def get_parser(argv=None):
                    help="test: also report the metrics at another threshold: a probability in (0, 1) "
                         "(snapped to k / B), or val-dice / val-image-dice to let the validation split "
                         "pick the threshold of the best global / mean per-image Dice (not with --tta)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if not 0 <= args.overlay_alpha <= 256:
+        p.error(f"--overlay_alpha must be in 0..256, got {args.overlay_alpha}")
+    if args.mode == "predict":
+        e = predict_args_error(args, int(os.environ.get("WORLD_SIZE", "1")))
+        if e:
+            p.error(e)
+    return args
+
+
+def predict_args_error(args, world=1):
+    """What --mode predict refuses, as a message (None: nothing)."""
+    from unet_hip.predict import check_predict_options
+    if world > 1:
+        return "--mode predict is single-process; launch it without torchrun"
+    if not args.input_dir or not args.output_dir:
+        return "--mode predict needs --input_dir and --output_dir"
+    if not args.checkpoint_path:
+        return "--mode predict needs --checkpoint_path: it segments with trained weights only"
+    try:
+        check_predict_options(args.tta, args.threshold)
+    except ValueError as e:
+        return f"--mode predict: {e}"
+    return None
+
+
+def build_model(args):
+    if args.model_type == "ResUNet":
+        return ResUNet(base_filters=args.base_filters, depth=args.depth, mfma_dtype=args.mfma)
+    if args.model_type == "ModUNet":
+        return ModUNet(base_filters=args.base_filters, depth=args.depth, mfma_dtype=args.mfma)
+    if args.mfma != "fp32":
+        raise SystemExit("--mfma bf16: models/model.py UNet has no bf16 path (UNET_ERR_UNSUPPORTED); "
+                         "use --model_type ModUNet or ResUNet")
+    return UNet()
+
+
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
+
+
+def same_stem(names):
+    """The file names of ``names`` whose stem another one has too (their outputs would collide)."""
+    stems = [os.path.splitext(n)[0] for n in names]
+    return [n for n, st in zip(names, stems) if stems.count(st) > 1]
+
+
+def predict(args):
+    """--mode predict: every image file of --input_dir through unet_hip.Predictor in batches of
+    --batch_size; masks, overlays and predictions.csv into --output_dir."""
+    from PIL import Image
+
+    from unet_hip.predict import CSV_HEADER, Predictor, save_predictions
+    if args.model_type not in ("UNet", "ModUNet", "ResUNet"):
+        raise SystemExit(f"model_type {args.model_type!r}: the HIP path has UNet, ModUNet and ResUNet")
+    set_seed(seed=42)
+    device = torch.device("cuda", torch.cuda.current_device())
+    model = build_model(args)
+    if not os.path.isfile(args.checkpoint_path):
+        raise SystemExit(f"--checkpoint_path {args.checkpoint_path!r}: no such file")
+    model.load_state_dict(torch.load(args.checkpoint_path, weights_only=True))
+    names = sorted(n for n in os.listdir(args.input_dir) if n.lower().endswith(IMAGE_SUFFIXES))
+    if not names:
+        raise SystemExit(f"--input_dir {args.input_dir!r} holds no image file ({', '.join(IMAGE_SUFFIXES)})")
+    clash = same_stem(names)
+    if clash:  # <stem>_mask.png of one would overwrite the other's
+        raise SystemExit(f"--input_dir {args.input_dir!r}: files share a stem and would share their outputs: "
+                         f"{', '.join(clash)}")
+    os.makedirs(args.output_dir, exist_ok=True)
+    pred = Predictor(model, args.image_size, device, tta=args.tta, tta_merge=args.tta_merge,
+                     threshold=args.threshold,
+                     pp=dict(keep_largest=args.pp_largest, min_area=args.pp_min_area, fill_holes=args.pp_fill_holes,
+                             connectivity=args.pp_connectivity),
+                     width=args.contour_width, alpha=args.overlay_alpha, bins=args.curve_bins)
+    lines = [",".join(CSV_HEADER)]
+    for start in range(0, len(names), args.batch_size):
+        chunk = names[start:start + args.batch_size]
+        planes = [decode_u8(Image.open(os.path.join(args.input_dir, n))) for n in chunk]
+        out = pred(planes, return_scores=args.save_prob)
+        lines += save_predictions(out, chunk, args.output_dir, save_scores=args.save_prob)
+    with open(os.path.join(args.output_dir, "predictions.csv"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"[PREDICT] {len(names)} images -> {args.output_dir}")
 
 
 def main(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.mode == "predict":
+        e = predict_args_error(args, world)
+        if e:
+            raise SystemExit(e)
+        from unet_hip import HipError
+        try:
+            return predict(args)
+        except (HipError, ValueError) as e:
+            raise SystemExit(f"--mode predict: {e}")
     if world > 1 and not torch.distributed.is_initialized():
         local = int(os.environ.get("LOCAL_RANK", "0"))
         torch.cuda.set_device(local)
@@ -209,15 +316,7 @@ def main(args):
     if args.use_amp_autocast:  # parsed and ignored, as before
         logger.info("--use_amp_autocast is ignored; the reduced-precision mode of this path is "
                     "--mfma bf16")
-    if args.model_type == "ResUNet":
-        model = ResUNet(base_filters=args.base_filters, depth=args.depth, mfma_dtype=args.mfma)
-    elif args.model_type == "ModUNet":
-        model = ModUNet(base_filters=args.base_filters, depth=args.depth, mfma_dtype=args.mfma)
-    elif args.mfma != "fp32":
-        raise SystemExit("--mfma bf16: models/model.py UNet has no bf16 path (UNET_ERR_UNSUPPORTED); "
-                         "use --model_type ModUNet or ResUNet")
-    else:
-        model = UNet()
+    model = build_model(args)
     if args.mfma != "fp32":  # a width the library refuses: its message now, no fallback
         from unet_hip.runtime import UNetRuntime
         try:

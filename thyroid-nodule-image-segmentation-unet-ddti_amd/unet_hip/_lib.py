@@ -130,6 +130,15 @@ SIGNATURES = {
                                      c_void_p]),
     "unet_curve_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "unet_curve_stats_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "unet_resize_f32_plan": (c_int, [c_int, c_int, c_void_p, c_void_p, P(c_int)]),
+    "unet_resize_f32_mask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "unet_resize_f32_mask_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                          c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "unet_overlay_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                c_void_p, c_void_p]),
+    "unet_overlay_u8_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                     c_void_p]),
     "unet_num_buckets": (c_int, [c_void_p, P(c_int)]),
     "unet_bucket_range": (c_int, [c_void_p, c_int, P(c_int64), P(c_int64)]),
     "unet_stream_wait_bucket": (c_int, [c_void_p, c_int, c_void_p]),

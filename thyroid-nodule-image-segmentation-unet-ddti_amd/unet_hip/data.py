@@ -254,6 +254,10 @@ class GpuResizeToTensor:
             raise ValueError("expected an (H, W) uint8 image (decoded 'L' mode)")
         return t.to(self.device, non_blocking=True).contiguous()
 
+    def upload(self, img):
+        """One decoded (H, W) uint8 frame on the device (a device tensor is returned as it is)."""
+        return self._upload(img)
+
     def _scratch(self, k, h, w):
         """Intermediate plane k of the reused device buffer: 0 / 1 the point and CLAHE launches,
         2 / 3 the elastic image / mask."""
@@ -313,9 +317,11 @@ class GpuResizeToTensor:
             t = d
         return t
 
-    def resize(self, img, out=None, aug=None, is_mask=False, elastic_done=False):
-        """One HxW uint8 image -> (oh, ow) fp32 in [0, 1] on the device."""
-        nearest = getattr(img, "resample", "bilinear") == "nearest"
+    def resize(self, img, out=None, aug=None, is_mask=False, elastic_done=False, nearest=None):
+        """One HxW uint8 image -> (oh, ow) fp32 in [0, 1] on the device.  nearest: the resample of
+        the plane when it no longer carries its ``resample`` tag (an uploaded tensor)."""
+        if nearest is None:
+            nearest = getattr(img, "resample", "bilinear") == "nearest"
         t = self._upload(img)
         if aug is not None:
             t = self.augment(t, aug, is_mask, elastic_done)

@@ -15,6 +15,8 @@
   on the device (``distance_maps``: the exact Euclidean distance transform kernels); its
   backward is one dlogits kernel weighted by the incoming gradient, again with no host sync.
 """
+import functools
+
 import torch
 import torch.distributed as dist
 
@@ -642,3 +644,122 @@ def curve_predict(logits, k, edges):
     if k >= B:
         return torch.zeros_like(logits, dtype=torch.bool)
     return logits > edges[k - 1]
+
+
+# ---------------------------------------------------------------- predict-mode export
+EXPORT_KINDS = {"sigmoid": 0, "greater": 1}
+OVERLAY_FIELDS = ("area", "contour", "x0", "y0", "x1", "y1")
+
+
+def resize_f32_plan(in_size, out_size):
+    """Pillow's BILINEAR plan of one axis for mode "F" images (unet_resize_f32_plan, a host
+    function): float64 coefficients (out, ksize) and int32 bounds (out, 2) = {first, count}."""
+    import ctypes
+
+    import numpy as np
+
+    from . import _lib
+    lib = _lib.load()
+    ks = ctypes.c_int()
+    _lib.check(lib.unet_resize_f32_plan(int(in_size), int(out_size), None, None, ctypes.byref(ks)), None,
+               "unet_resize_f32_plan")
+    k = np.zeros((out_size, ks.value), np.float64)
+    b = np.zeros((out_size, 2), np.int32)
+    _lib.check(lib.unet_resize_f32_plan(int(in_size), int(out_size), k.ctypes.data, b.ctypes.data,
+                                        ctypes.byref(ks)), None, "unet_resize_f32_plan")
+    return k, b
+
+
+@functools.lru_cache(maxsize=64)
+def _host_plan(n_in, n_out):
+    """(coeffs, bounds, ksize) as CPU tensors for the host twin, a bounded cache per (in, out)."""
+    k, b = resize_f32_plan(n_in, n_out)
+    return torch.from_numpy(k), torch.from_numpy(b), k.shape[1]
+
+
+def _export_resize_args(score, size, kind, threshold):
+    if score.dim() != 2 or score.shape[0] < 1 or score.shape[1] < 1:
+        raise ValueError(f"score must be one (S_h, S_w) plane, got {tuple(score.shape)}")
+    if kind not in EXPORT_KINDS:
+        raise ValueError(f"kind must be one of {sorted(EXPORT_KINDS)}, got {kind!r}")
+    oh, ow = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if oh < 1 or ow < 1:
+        raise ValueError(f"size must be positive, got {(oh, ow)}")
+    score = score.detach()
+    if not (score.dtype == torch.float32 and score.is_contiguous()):
+        score = score.float().contiguous()
+    return score, oh, ow, EXPORT_KINDS[kind], float(threshold)
+
+
+def resize_back(score, size, kind="sigmoid", threshold=0.5, return_plane=False):
+    """One (S_h, S_w) score plane resized back to ``size`` = (h, w) on the device and the current
+    stream, bit for bit ``PIL.Image.fromarray(score, "F").resize((w, h), BILINEAR)``, and
+    thresholded there in the same pass: the uint8 {0, 1} mask (h, w), and the float32 plane when
+    ``return_plane`` (otherwise it is never written).  The axis plans are cached on the device's
+    runtime per (in, out), at most ``UNetRuntime.EXPORT_PLAN_CACHE`` of them.  kind "sigmoid": sigmoid(v) > 0.5 as
+    ``Trainer.test`` reads logits (threshold ignored); "greater": v > threshold (a probability plane
+    at 0.5, or logits against an edge of ``curve_edges``)."""
+    rt = _boundary_runtime(score, "resize_back")
+    score, oh, ow, k, thr = _export_resize_args(score, size, kind, threshold)
+    h, w = score.shape
+    mask, plane = rt.resize_f32_mask(score, oh, ow, rt.export_plan(w, ow), rt.export_plan(h, oh), k, thr,
+                                     bool(return_plane))
+    return (mask, plane) if return_plane else mask
+
+
+def resize_back_host(score, size, kind="sigmoid", threshold=0.5, return_plane=False):
+    """``resize_back`` of a CPU tensor through the library's host twin."""
+    _cc_cpu(score, "resize_back_host")
+    score, oh, ow, k, thr = _export_resize_args(score, size, kind, threshold)
+    h, w = score.shape
+    kh, bh, ksh = _host_plan(w, ow) if w != ow else (None, None, 0)
+    kv, bv, ksv = _host_plan(h, oh) if h != oh else (None, None, 0)
+    mask = torch.empty((oh, ow), dtype=torch.uint8)
+    plane = torch.empty((oh, ow), dtype=torch.float32) if return_plane else None
+    _cc_host_call("unet_resize_f32_mask_host", score, h, w, oh, ow, kh, bh, ksh, kv, bv, ksv, k, thr, plane, mask)
+    return (mask, plane) if return_plane else mask
+
+
+def _overlay_args(gray, pred, gt, width, alpha):
+    def plane(t, what):
+        t = t.detach()
+        if t.dtype == torch.bool:
+            t = t.to(torch.uint8)
+        if t.dtype != torch.uint8 or t.dim() != 2:
+            raise ValueError(f"{what} must be an (H, W) uint8 plane, got {t.dtype} {tuple(t.shape)}")
+        return t.contiguous()
+    gray, pred = plane(gray, "gray"), plane(pred, "pred")
+    gt = None if gt is None else plane(gt, "gt")
+    if gray.numel() == 0:
+        raise ValueError(f"gray holds no pixel: {tuple(gray.shape)}")
+    for t, what in ((pred, "pred"), (gt, "gt")):
+        if t is not None and (t.shape != gray.shape or t.device != gray.device):
+            raise ValueError(f"{what} must be {tuple(gray.shape)} on {gray.device}")
+    width, alpha = int(width), int(alpha)
+    if not 1 <= width <= 3:
+        raise ValueError(f"width must be 1, 2 or 3, got {width}")
+    if not 0 <= alpha <= 256:
+        raise ValueError(f"alpha must be in 0..256, got {alpha}")
+    return gray, pred, gt, width, alpha
+
+
+def overlay(gray, pred, gt=None, width=1, alpha=0):
+    """The contour overlay of one frame on the device: (rgb uint8 (H, W, 3), stats int64 (6,)).
+    gray: the (H, W) uint8 frame; pred / gt: (H, W) uint8 or bool masks, nonzero foreground.  The
+    inside of pred is tinted red at alpha / 256 (0: none), the contour of gt (when given) is solid
+    blue and that of pred solid red on top; a contour of ``width`` in 1..3 holds the foreground
+    pixels within that city-block distance of a background pixel or of the frame.  stats =
+    {area, contour pixels, x0, y0, x1, y1} of pred, the box inclusive, -1 when pred is empty."""
+    rt = _boundary_runtime(gray, "overlay")
+    return rt.overlay_u8(*_overlay_args(gray, pred, gt, width, alpha))
+
+
+def overlay_host(gray, pred, gt=None, width=1, alpha=0):
+    """``overlay`` of CPU tensors through the library's host twin."""
+    _cc_cpu(gray, "overlay_host")
+    gray, pred, gt, width, alpha = _overlay_args(gray, pred, gt, width, alpha)
+    h, w = gray.shape
+    rgb = torch.empty((h, w, 3), dtype=torch.uint8)
+    stats = torch.empty(6, dtype=torch.int64)
+    _cc_host_call("unet_overlay_u8_host", gray, pred, gt, h, w, width, alpha, rgb, stats)
+    return rgb, stats

@@ -5,6 +5,7 @@ parameter / BN-buffer tables (so the ``nn.Module`` can lay its tensors out in th
 arenas the kernels read) and thin, shape-checked wrappers of the C entry points that
 take torch tensors and enqueue on torch's current stream.
 """
+import collections
 import ctypes
 
 import torch
@@ -297,6 +298,51 @@ class UNetRuntime:
                                        _lib.ptr(dice_sum), _lib.stream_ptr(plane_hist.device))
         _lib.check(rc, self.ctx, "unet_curve_stats")
         return out
+
+    EXPORT_PLAN_CACHE = 256  # axis plans kept per runtime (the least recently used leaves)
+
+    def export_plan(self, n_in, n_out):
+        """(coeffs float64, bounds int32, ksize) of unet_resize_f32_plan on this runtime's device,
+        cached per (in, out); None for an unchanged axis."""
+        if n_in == n_out:
+            return None
+        cache = self.__dict__.setdefault("_export_plans", collections.OrderedDict())
+        key = (int(n_in), int(n_out))
+        if key in cache:
+            cache.move_to_end(key)
+            return cache[key]
+        from .functional import resize_f32_plan
+        k, b = resize_f32_plan(*key)
+        cache[key] = (torch.from_numpy(k).to(self.device), torch.from_numpy(b).to(self.device), k.shape[1])
+        while len(cache) > self.EXPORT_PLAN_CACHE:
+            cache.popitem(last=False)
+        return cache[key]
+
+    def resize_f32_mask(self, src, oh, ow, plan_h, plan_v, kind, thr, want_plane):
+        """mask uint8 (oh, ow) and, when wanted, the float32 plane (oh, ow) of src (h, w) resized as
+        Pillow resizes a mode "F" image (unet_resize_f32_mask).  plan_h / plan_v: (coeffs, bounds,
+        ksize) on the device for w -> ow / h -> oh, None for an unchanged axis."""
+        h, w = src.shape
+        mask = torch.empty((oh, ow), dtype=torch.uint8, device=src.device)
+        plane = torch.empty((oh, ow), dtype=torch.float32, device=src.device) if want_plane else None
+        kh, bh, ksh = plan_h or (None, None, 0)
+        kv, bv, ksv = plan_v or (None, None, 0)
+        rc = self.lib.unet_resize_f32_mask(self.ctx, _lib.ptr(src), h, w, oh, ow, _lib.ptr(kh), _lib.ptr(bh), ksh,
+                                           _lib.ptr(kv), _lib.ptr(bv), ksv, kind, float(thr), _lib.ptr(plane),
+                                           _lib.ptr(mask), _lib.stream_ptr(src.device))
+        _lib.check(rc, self.ctx, "unet_resize_f32_mask")
+        return mask, plane
+
+    def overlay_u8(self, gray, pred, gt, r, alpha):
+        """rgb uint8 (h, w, 3) and stats int64 (6,) {area, contour pixels, x0, y0, x1, y1} of the
+        uint8 planes gray, pred and gt (or None), each (h, w) (unet_overlay_u8)."""
+        h, w = gray.shape
+        rgb = torch.empty((h, w, 3), dtype=torch.uint8, device=gray.device)
+        stats = torch.empty(6, dtype=torch.int64, device=gray.device)
+        rc = self.lib.unet_overlay_u8(self.ctx, _lib.ptr(gray), _lib.ptr(pred), _lib.ptr(gt), h, w, int(r),
+                                      int(alpha), _lib.ptr(rgb), _lib.ptr(stats), _lib.stream_ptr(gray.device))
+        _lib.check(rc, self.ctx, "unet_overlay_u8")
+        return rgb, stats
 
     def stream_wait_bucket(self, b, stream):
         rc = self.lib.unet_stream_wait_bucket(self.ctx, b, ctypes.c_void_p(stream.cuda_stream))

@@ -47,6 +47,11 @@ What runs where (MI355X-first):
   (a float in (0, 1), snapped to k / B, or ``"val-dice"`` / ``"val-image-dice"``: the same sweep over
   the validation split decides) adds an ``OPT_*`` block of the confusion metrics at that threshold;
   every other block keeps reading the 0.5 mask.
+* ``test(save_overlays=True)`` (``config.save_overlays``): every test sample's contour overlay is
+  rendered on the device (``unet_hip.overlay``: prediction red on top of ground truth blue, at the
+  network resolution; ``config.contour_width`` / ``config.overlay_alpha``) and written by rank 0 as
+  ``test_overlay_<index>.png``, in the sample order of the contour plot (utils/trainer.py:262-299),
+  which needs matplotlib and scikit-image where this needs only Pillow.  The metrics are unchanged.
 """
 import os
 import random
@@ -314,10 +319,14 @@ class Trainer:
         self.writer.close()
 
     @torch.no_grad()
-    def test(self):
+    def test(self, save_overlays=None):
         """Global pixel TP/FP/FN/TN over the test set (utils/trainer.py:206-260); counts are
         accumulated on the device.  The contour-overlay PNGs (:262-299) are written only when
-        matplotlib and scikit-image are importable."""
+        matplotlib and scikit-image are importable; ``save_overlays`` (default
+        ``config.save_overlays``) writes one device-rendered ``test_overlay_<index>.png`` per sample
+        whether they are or not."""
+        if save_overlays is None:
+            save_overlays = bool(getattr(self.config, "save_overlays", False))
         self.logger.info("------------------Starting Testing Model------------------")
         self.model.eval()
         if self.ddp is not None:  # every shard evaluated with replica 0's BN buffers (DataParallel)
@@ -512,7 +521,7 @@ class Trainer:
             self.logger.info(omsg)
             m.update({"OPT_" + k: v for k, v in om.items()})
             m["OPT_Threshold"] = opt_k / bins
-        if _distributed() and self._can_plot():
+        if _distributed() and (self._can_plot() or save_overlays):
             # one set of PNGs over the whole test set, in the reference's sample order: batch
             # by batch, each batch's shards in rank order (DataParallel's gather order)
             # (gather to rank 0 only: it alone plots, so the other ranks need no copies)
@@ -523,7 +532,29 @@ class Trainer:
         keep = [k for k in keep if k is not None]
         if keep and self.rank0:
             self._plot_contours(keep)
+        if save_overlays and self.rank0:
+            self._save_overlays(keep)
         return m
+
+    def _save_overlays(self, keep):
+        """One PNG per kept sample (images, targets, predicted mask as CPU batches), rendered on the
+        device: the frame's bytes, the ground-truth contour in blue, the prediction's in red."""
+        from PIL import Image
+
+        from unet_hip.predict import gray_u8
+        cfg = self.config
+        width = int(getattr(cfg, "contour_width", 1) or 1)
+        alpha = int(getattr(cfg, "overlay_alpha", 0) or 0)
+        idx = 0
+        for images, masks, mask in keep:
+            gray = gray_u8(images.to(self.device))
+            gt = (masks[:, 0].to(self.device).to(torch.uint8) == 1).to(torch.uint8)
+            pr = mask[:, 0].to(self.device)
+            for n in range(gray.shape[0]):
+                rgb, _ = unet_hip.overlay(gray[n], pr[n], gt[n], width, alpha)
+                Image.fromarray(rgb.cpu().numpy(), "RGB").save(
+                    os.path.join(cfg.result_dir, f"test_overlay_{idx}.png"))
+                idx += 1
 
     # ---- threshold sweep: device-side accumulators, read once ----
     def _curve_acc(self, bins):
