@@ -126,6 +126,47 @@ def test_mod_full_grads_vs_oracle():
     assert errs[worst] <= GRAD_TOL, f"{worst}: {errs[worst]:.3e}"
 
 
+def test_mod_wide_f32_dz_pass_vs_fp64():
+    """The f32 in-place dz pass past 1024 channels: UNet(base 256, depth 3), f32, x3 = 0, N = 1,
+    64 x 64.  The bottleneck convs have 2048 outputs at 8 x 8 (C / 4 = 512 quads: two trips of
+    the kernel's quad loop, one row per pass), the level-2 convs 1024 (exactly 256 quads).  One
+    training step against the oracle in fp64, at the bars of test_mod_full_grads_vs_oracle,
+    and the step shows a bn_dz launch in front of each of those layers' weight gradients."""
+    import unet_hip
+    base, depth = 256, 3
+    P = MO.make_params(42, base, depth)
+    x, t = inputs(3, 1, 64, 64)
+    ref = MO.train_step(_to64(P), _to64(MO.init_buffers(base, depth)), None, x.double(), t.double(), depth=depth)
+    m = hip_mod_model(P, DEV, base, depth)
+    rt = m.flatten_().rt
+    with options(rt, x3=0):
+        rt.timing(True)
+        try:
+            logits = m(x.to(DEV))
+            losses = unet_hip.seg_losses(logits, t.to(DEV))
+            (losses[0] + losses[1]).backward()
+            torch.cuda.synchronize()
+            labels = [lab for lab, _, _ in rt.timing_records()]
+        finally:
+            rt.timing(False)
+    # a conv's bn_dz launch comes before its weight gradient, whose label carries the layer
+    dz_layers, pending = set(), False
+    for lab in labels:
+        if lab == "bn_dz":
+            pending = True
+        elif lab.startswith("conv_wgrad/") and pending:
+            dz_layers.add(int(lab.rpartition("|")[2]))
+            pending = False
+    wide = {2 * b + j for b in (2, 3, 4) for j in (0, 1)}  # level 2 (C = 1024), bottleneck (2048)
+    assert wide <= dz_layers, f"no bn_dz launch for convs {sorted(wide - dz_layers)}: {labels}"
+    lerr = rel_max(logits.detach().cpu().numpy(), ref["logits"].numpy())
+    errs = grad_errors(m, ref["grads"])
+    worst = max(errs, key=errs.get)
+    print(f"wide f32 dz pass: logits {lerr:.3e}, worst gradient {worst} {errs[worst]:.3e}")
+    assert lerr <= LOGIT_TOL
+    assert errs[worst] <= GRAD_TOL, f"{worst}: {errs[worst]:.3e}"
+
+
 def test_mod_config4_architecture(golden_dir):
     """The config-4 network (base 128, depth 5, 497 M params; 2048 / 4096-channel
     bottleneck) at B=2 64x64, one step vs the reference's fixture."""

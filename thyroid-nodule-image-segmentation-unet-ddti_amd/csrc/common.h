@@ -10,7 +10,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // BN(+ReLU) backward value dz = A do + B (y - mean) + C in one explicit rounding order,
-// shared by every kernel that forms it (the bn_dz passes, the OP_DZ GEMM loaders,
+// shared by every kernel that forms it (the dz pass of dz_pass.h, the OP_DZ GEMM loaders,
 // conv_first_wgrad): left to -ffp-contract, hipcc contracted the same source expression
 // differently per kernel, and the fused-loader and materialised paths disagreed in the last
 // bit.
@@ -207,19 +207,7 @@ int wgrad_x3_tile_dims(int tile, int* bm, int* bn);
 // channel offset doff
 int k_to_x3(const float* src, int ld, int off, int C, const float* scale, const float* shift,
             int relu, int64_t P, uint16_t* dst, int dld, int doff, hipStream_t s);
-// BN-backward dz (bn_dz4) as an x3 image; bpart (optional): [x3_dz_blocks(P)][C] column sums
-// hdl != null (r05): `d` is not read; do = [hrelu: fma(y, hsc, hsh) > 0] hdl[m] hw[c] (the 1x1
-// head's backward with one output channel, head_bwd's expression)
-int k_bn_dz_x3(const float* d, const float* y, int ld, int off, int64_t P, int C, const float* coef,
-               int mask, uint16_t* dz3, float* bpart, hipStream_t s, const float* hdl = nullptr,
-               const float* hw = nullptr, const float* hsc = nullptr, const float* hsh = nullptr,
-               int hrelu = 0);
-// the same with do = [msc: fma(msc, y, msh) > 0] (dskip + [idx == window position] dp): the
-// encoder block's second conv, maxpool_bwd's expression (r05; dskip offset applied, N H W the
-// full-resolution grid, P = N H W < 2^24 for the f32-reciprocal pixel decode)
-int k_bn_dz_x3_pool(const float* y, int ld, int off, int64_t P, int C, const float* coef, int mask,
-                    uint16_t* dz3, float* bpart, const float* dp, const uint8_t* idx, const float* dskip,
-                    int ldskip, const float* msc, const float* msh, int N, int H, int W, hipStream_t s);
+// row blocks of the dz pass's x3 output (dz_pass.h): the rows of its bias column partials
 int x3_dz_blocks(int64_t P);
 // register-staged bf16 wgrad tile ids (a.bf16): 0 = 128x128/32 px, 2 = 64x64/64,
 // 3 = 128x64/64, 4 = 64x128/64

@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "dz_pass.h"
 #include "gemm_common.h"
 
 namespace {
@@ -1143,7 +1144,7 @@ __device__ __forceinline__ void x3_store8(const float (&v)[8], uint16_t* d) {
 
 // Rows per block of the two image passes: 256, or fewer where that leaves the grid short of
 // ~1024 blocks (the deep levels: 8k rows x 1024 channels made 32 blocks, 1.2 TB/s;
-// profiles/r05_x3_pass_exp.txt).  bn_dz_x3's bias partials come one row per block, so the
+// profiles/r05_x3_pass_exp.txt).  bn_dz_x3_kernel's bias partials come one row per block, so the
 // caller sizes its reduction with x3_dz_blocks (the same rule).
 __host__ __device__ inline int x3_rows_per_block(int64_t P) {
     return P >= 256 * 1024 ? 256 : P >= 128 * 1024 ? 128 : 64;
@@ -1210,40 +1211,18 @@ __global__ __launch_bounds__(256) void to_x3_kernel(const float* __restrict__ sr
     }
 }
 
-// dz = [!mask || y > 0] (A do + B (y - mean) + C) per channel (bn_dz4, the f32 path's
-// rounding order) as the x3 image dz3 [P][C / 32][3][32]; with bpart, also the per-block
+// The dz pass (dz_pass.h: `do` from memory, the head or the pool) writing the x3 image dz3
+// [P][C / 32][3][32]; with bpart, also the per-block
 // column sums of dz (the conv bias gradient; k_sum_partials adds the G rows in f64).  A
 // block covers rpb rows (x3_rows_per_block); thread t handles channel octet t % (C / 8) of
 // rows t / (C / 8) + k 256 / (C / 8), X3_RIF rows in flight (the column sums add each thread's
 // rows in ascending order).
-// HEAD (r05): the last conv's `do` is not read from memory but recomputed from the 1x1 head:
-// do[m][c] = [BN->ReLU: fma(y, sc, sh) > 0] dl[m] w[c] (head_bwd's expression, bit for bit;
-// out_channels = 1), so head_bwd need not store the 64-channel f32 do at full resolution.
-struct DzHead {
-    const float* dl;     // d logits [P] (NCHW with one channel = pixel order)
-    const float* w;      // head weights [C]
-    const float *sc, *sh;  // the last BN's forward affine
-    int relu;            // BN -> ReLU: mask by the activation
-};
-// POOL (r05): the encoder block's second conv: do = [BN->ReLU: fma(msc, y, msh) > 0] (dskip +
-// [winner == window position] dp) -- maxpool_bwd's expression, so it need not store do
-struct DzPool {
-    const float* dp;       // d pooled [N][H/2][W/2][C]
-    const uint8_t* idx;    // winner index per pooled element
-    const float* dskip;    // the concat gradient's skip half (offset applied), row stride ldskip
-    int ldskip;
-    const float *msc, *msh;  // BN -> ReLU mask affine, or null
-    int H, W;              // full-resolution grid
-    float rH, rW;
-};
-
 template <int SRC>  // 0: do from memory, 1: DzHead, 2: DzPool
 __global__ __launch_bounds__(256) void bn_dz_x3_kernel(const float* __restrict__ d, const float* __restrict__ y,
                                                        int ld, int off, int64_t P, int C,
                                                        const float* __restrict__ coef, int mask,
                                                        uint16_t* __restrict__ dz3, float* __restrict__ bpart,
                                                        int rpb, DzHead hd, DzPool pl) {
-    constexpr bool HEAD = SRC == 1, POOL = SRC == 2;
     __shared__ float red[256 * 8];
     const int g8 = C / 8, G = min(g8, 256);  // octets per pass (bias sums: C <= 2048, one pass)
     const int r0 = threadIdx.x / G, rstep = 256 / G;
@@ -1253,91 +1232,27 @@ __global__ __launch_bounds__(256) void bn_dz_x3_kernel(const float* __restrict__
     float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int oct = threadIdx.x % G; active && oct < g8; oct += G) {
         const int c = oct * 8;
-        f32x4 ka[2], kb[2], kc[2], km[2], hw[2], hs[2], hh[2], msc[2], msh[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            if (POOL && pl.msc) {  // the BN -> ReLU mask affine, in registers (r06)
-                msc[h] = *(const f32x4*)(pl.msc + c + 4 * h);
-                msh[h] = *(const f32x4*)(pl.msh + c + 4 * h);
-            }
-            ka[h] = *(const f32x4*)(coef + c + 4 * h);
-            kb[h] = *(const f32x4*)(coef + C + c + 4 * h);
-            kc[h] = *(const f32x4*)(coef + 2 * C + c + 4 * h);
-            km[h] = *(const f32x4*)(coef + 3 * C + c + 4 * h);
-            if constexpr (HEAD) {
-                hw[h] = *(const f32x4*)(hd.w + c + 4 * h);
-                hs[h] = *(const f32x4*)(hd.sc + c + 4 * h);
-                hh[h] = *(const f32x4*)(hd.sh + c + 4 * h);
-            }
-        }
+        const DzCoef k = dz_coef(coef, C, c);
+        const DzSrcCoef sk = dz_src_coef<SRC>(hd, pl, c);
         for (int64_t m = mb + r0; m < me; m += X3_RIF * rstep) {
-            f32x4 dv[X3_RIF][2], yv[X3_RIF][2];
-            float dl[X3_RIF];
-            f32x4 gp[X3_RIF][2];
-            uint32_t wi[X3_RIF][2];
-            int kk[X3_RIF];
+            DzRow r[X3_RIF];
 #pragma unroll
             for (int i = 0; i < X3_RIF; ++i) {
                 const int64_t mi = m + i * rstep;
-                if (mi < me) {
-                    if constexpr (HEAD) dl[i] = hd.dl[mi];
-                    int64_t po = 0;
-                    if constexpr (POOL) {
-                        const Pix q = decode_fast((int)mi, pl.H, pl.W, pl.rH, pl.rW);
-                        po = ((int64_t)q.img * (pl.H >> 1) + (q.y >> 1)) * (pl.W >> 1) + (q.x >> 1);
-                        kk[i] = (q.y & 1) * 2 + (q.x & 1);
-                        const uint2 w2 = *(const uint2*)(pl.idx + po * C + c);
-                        wi[i][0] = w2.x;
-                        wi[i][1] = w2.y;
-                    }
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        if constexpr (POOL) {
-                            dv[i][h] = *(const f32x4*)(pl.dskip + mi * pl.ldskip + c + 4 * h);
-                            gp[i][h] = *(const f32x4*)(pl.dp + po * C + c + 4 * h);
-                        } else if constexpr (!HEAD) {
-                            dv[i][h] = *(const f32x4*)(d + mi * C + c + 4 * h);
-                        }
-                        yv[i][h] = *(const f32x4*)(y + mi * ld + off + c + 4 * h);
-                    }
-                }
-            }
-            if constexpr (POOL) {
-#pragma unroll
-                for (int i = 0; i < X3_RIF; ++i)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if (((wi[i][h] >> (8 * j)) & 0xFF) == (uint32_t)kk[i]) dv[i][h][j] += gp[i][h][j];
-                            if (pl.msc && !bn_relu_on(yv[i][h][j], msc[h][j], msh[h][j]))
-                                dv[i][h][j] = 0.f;
-                        }
-            }
-            if constexpr (HEAD) {
-#pragma unroll
-                for (int i = 0; i < X3_RIF; ++i)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const bool on = !hd.relu || bn_relu_on(yv[i][h][j], hs[h][j], hh[h][j]);
-                            dv[i][h][j] = on ? dl[i] * hw[h][j] : 0.f;
-                        }
+                if (mi < me) dz_load<SRC>(r[i], d, y, ld, off, C, mi, c, hd, pl);
             }
 #pragma unroll
             for (int i = 0; i < X3_RIF; ++i) {
                 const int64_t mi = m + i * rstep;
                 if (mi >= me) break;
+                f32x4 o[2];
+                dz_form<SRC>(r[i], k, sk, mask, hd, pl, o);
                 float v[8];
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const f32x4 r = bn_dz4(ka[h], dv[i][h], kb[h], yv[i][h], km[h], kc[h]);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[4 * h + j] = (!mask || yv[i][h][j] > 0.f) ? r[j] : 0.f;
+                for (int j = 0; j < 8; ++j) {
+                    v[j] = o[j >> 2][j & 3];
+                    cs[j] += v[j];
                 }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) cs[j] += v[j];
                 x3_store8(v, dz3 + mi * 3 * (int64_t)C + (c >> 5) * 96 + (c & 31));
             }
         }
@@ -1471,29 +1386,17 @@ int x3_dz_blocks(int64_t P) {
     return (int)((P + rpb - 1) / rpb);
 }
 
-int k_bn_dz_x3(const float* d, const float* y, int ld, int off, int64_t P, int C, const float* coef,
-               int mask, uint16_t* dz3, float* bpart, hipStream_t s, const float* hdl, const float* hw,
-               const float* hsc, const float* hsh, int hrelu) {
-    if (C % 32 || (bpart && C > 2048) || ld % 4 || off % 4 || P < 1) return -1;
-    if (hdl) {
-        if (!hw || !hsc || !hsh) return -1;
-        const DzHead hd{hdl, hw, hsc, hsh, hrelu};
-        hipLaunchKernelGGL(bn_dz_x3_kernel<1>, dim3(x3_dz_blocks(P)), dim3(256), 0, s, d, y, ld, off, P, C,
-                           coef, mask, dz3, bpart, x3_rows_per_block(P), hd, DzPool{});
-    } else {
-        hipLaunchKernelGGL(bn_dz_x3_kernel<0>, dim3(x3_dz_blocks(P)), dim3(256), 0, s, d, y, ld, off, P, C,
-                           coef, mask, dz3, bpart, x3_rows_per_block(P), DzHead{}, DzPool{});
-    }
-    return (int)hipGetLastError();
-}
-
-int k_bn_dz_x3_pool(const float* y, int ld, int off, int64_t P, int C, const float* coef, int mask,
-                    uint16_t* dz3, float* bpart, const float* dp, const uint8_t* idx, const float* dskip,
-                    int ldskip, const float* msc, const float* msh, int N, int H, int W, hipStream_t s) {
-    if (C % 32 || (bpart && C > 2048) || ld % 4 || off % 4 || ldskip % 4 || P < 1) return -1;
-    if (!dp || !idx || !dskip || H % 2 || W % 2 || (int64_t)N * H * W != P || P >= (1LL << 24)) return -1;
-    const DzPool pl{dp, idx, dskip, ldskip, msc, msh, H, W, 1.f / (float)H, 1.f / (float)W};
-    hipLaunchKernelGGL(bn_dz_x3_kernel<2>, dim3(x3_dz_blocks(P)), dim3(256), 0, s, nullptr, y, ld, off, P, C,
-                       coef, mask, dz3, bpart, x3_rows_per_block(P), DzHead{}, pl);
+int k_bn_dz_x3(const DzArgs& a, hipStream_t s) {
+    const dim3 grid(x3_dz_blocks(a.P));
+#define DZ_X3(SRC)                                                                                          \
+    hipLaunchKernelGGL(bn_dz_x3_kernel<SRC>, grid, dim3(256), 0, s, a.d, a.y, a.ld, a.off, a.P, a.C, a.coef, \
+                       a.mask, a.dz3, a.bpart, x3_rows_per_block(a.P), a.head, a.pool)
+    if (a.head.dl)
+        DZ_X3(1);
+    else if (a.pool.dp)
+        DZ_X3(2);
+    else
+        DZ_X3(0);
+#undef DZ_X3
     return (int)hipGetLastError();
 }

@@ -58,24 +58,11 @@ int k_maxpool_bwd(const float* dp, const uint8_t* idx, const float* dskip, int l
 int k_bn_bwd_finalize2(const float* part, int G, int C, double count, const float* gamma,
                        const float* mean, const float* invstd, float* coef, float* dgamma,
                        float* dbeta, hipStream_t s);
-int k_bn_dz(float* d, const float* y, int ld, int off, int64_t P, int C, const float* coef, int mask,
-            hipStream_t s);
+// (the dz pass between them: k_bn_dz, dz_pass.h)
 // bf16 image [P][dld] (dld 0 = C: dense) of op(src), channels [0, C), for the LDS-DMA GEMMs
 // (affine if scale, ReLU on c < relu)
 int k_to_bf16(const float* src, int ld, int off, int C, const float* scale, const float* shift,
               int relu, int64_t P, uint16_t* dst, hipStream_t s, int dld = 0);
-// bn_dz writing the dense bf16 image of dz (and the f32 dz in place when f32 != 0)
-// (r06) hdl != null (option head_fuse, one output channel): do = [hrelu: fma(y, hsc, hsh) > 0]
-// hdl[m] hw[c] recomputed from the head (d unused, f32 must be 0)
-int k_bn_dz16(float* d, const float* y, int ld, int off, int64_t P, int C, const float* coef,
-              int mask, uint16_t* dz16, int f32, hipStream_t s, const float* hdl = nullptr,
-              const float* hw = nullptr, const float* hsc = nullptr, const float* hsh = nullptr,
-              int hrelu = 0);
-// (r06) the same with `do` recomputed from the max-pool backward's inputs (option pool_fuse):
-// do = [msc: fma(msc, y, msh) > 0] (dskip + [idx == window position] dp); no f32 dz
-int k_bn_dz16_pool(const float* y, int ld, int off, int64_t P, int C, const float* coef, int mask,
-                   uint16_t* dz16, const float* dp, const uint8_t* idx, const float* dskip, int ldskip,
-                   const float* msc, const float* msh, int N, int H, int W, hipStream_t s);
 int k_bias_reduce(const float* slab, int S, int taps, int C, float* out, hipStream_t s);
 // ConvT bias partials [splits][4][C] from the up half of the concat gradient (LDS-DMA wgrad)
 int k_up2_bias_partials(const float* d, int ld, int off, int H, int W, int64_t P, int C, int pps,

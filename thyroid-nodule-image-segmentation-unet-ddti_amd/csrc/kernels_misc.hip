@@ -7,7 +7,7 @@
 // Layout everywhere: NHWC, channel stride `ld`, channel offset `off` (concat slices).
 #include "kernels_misc.h"
 #include "surf.h"  // surf_pred / surf_target_u8: the mask readout
-#include "gemm_common.h"  // Pix, decode, pix_advance (and x3_split.h)
+#include "dz_pass.h"  // and gemm_common.h: Pix, decode, pix_advance (and x3_split.h)
 
 namespace {
 
@@ -800,11 +800,8 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
                 f32x4 v = *(const f32x4*)(dskip + pin * ldskip + offskip + c);
                 const f32x4 yv = y ? *(const f32x4*)(y + pin * ldy + offy + c) : f32x4{0, 0, 0, 0};
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (((bi >> (8 * j)) & 0xFF) == (uint32_t)k) v[j] += gp[j];
-                    // (explicit fma: bn_dz_x3's fused pool source recomputes this mask, r05)
-                    if (mscale && !bn_relu_on(yv[j], ms[j], mb[j])) v[j] = 0.f;
-                }
+                for (int j = 0; j < 4; ++j)  // (the fused dz passes recompute it with the same helper)
+                    v[j] = dz_pool_do(v[j], gp[j], (bi >> (8 * j)) & 0xFF, k, mscale != nullptr, yv[j], ms[j], mb[j]);
                 if (dout) *(f32x4*)(dout + pin * C + c) = v;  // (null: the dz pass recomputes it)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -859,188 +856,66 @@ __global__ void bn_bwd_finalize2_kernel(const float* __restrict__ part, int G, i
 }
 
 
-// dz = A do + B (y - mean) + C in place, masked by [y > 0] when `mask` (ReLU before the BN).
-// Row form (C / 4 <= 256): each thread keeps one channel quad and its coefficients in
-// registers and walks pixel rows, so there is no per-element index division.
+// The dz pass (dz_pass.h) with f32 dz in place over the stored do.  Each thread keeps one
+// channel quad and its coefficients in registers and walks pixel rows, so there is no
+// per-element index division; C / 4 > 256 takes several quads per thread, one row per pass.
 __global__ __launch_bounds__(256) void bn_dz_rows_kernel(float* __restrict__ d,
                                                          const float* __restrict__ y, int ld,
                                                          int off, int64_t P, int C,
                                                          const float* __restrict__ coef, int mask) {
-    const int tpr = C / 4, rpp = 256 / tpr;
+    const int tpr = C / 4 < 256 ? C / 4 : 256, rpp = 256 / tpr;
     if ((int)threadIdx.x >= rpp * tpr) return;  // partial row group (tpr does not divide 256)
-    const int c = (threadIdx.x % tpr) * 4;
-    const f32x4 ka = *(const f32x4*)(coef + c), kb = *(const f32x4*)(coef + C + c),
-                kc = *(const f32x4*)(coef + 2 * C + c), km = *(const f32x4*)(coef + 3 * C + c);
-    for (int64_t m = (int64_t)blockIdx.x * rpp + threadIdx.x / tpr; m < P;
-         m += (int64_t)gridDim.x * rpp) {
-        f32x4* pd = (f32x4*)(d + m * C + c);
-        const f32x4 v = *(const f32x4*)(y + m * ld + off + c);
-        const f32x4 r = bn_dz4(ka, *pd, kb, v, km, kc);
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (!mask || v[j] > 0.f) ? r[j] : 0.f;
-        *pd = o;
+    for (int c = (threadIdx.x % tpr) * 4; c < C; c += tpr * 4) {
+        const f32x4 ka = *(const f32x4*)(coef + c), kb = *(const f32x4*)(coef + C + c),
+                    kc = *(const f32x4*)(coef + 2 * C + c), km = *(const f32x4*)(coef + 3 * C + c);
+        for (int64_t m = (int64_t)blockIdx.x * rpp + threadIdx.x / tpr; m < P;
+             m += (int64_t)gridDim.x * rpp) {
+            f32x4* pd = (f32x4*)(d + m * C + c);
+            *pd = dz_finish(mask, ka, *pd, kb, *(const f32x4*)(y + m * ld + off + c), km, kc);
+        }
     }
 }
 
-// bn_dz for the bf16 GEMMs: dz as the dense bf16 image the LDS-DMA dgrad / wgrad read
-// (round to nearest even, as k_to_bf16), and the f32 dz in place only when another consumer
-// still reads it (f32 != 0).  8 channels per thread.
-// POOL (r06, option pool_fuse on the bf16 path): `d` is not read; do = [fma(msc, y, msh) > 0]
-// (dskip + [winner == window position] dpool), the max-pool backward's sum recomputed from its
-// inputs (as kernels_gemm_x3.hip bn_dz_x3_kernel<2>), so maxpool_bwd stores no full-resolution do
-struct Dz16Pool {
-    const float* dp;       // d pooled [N][H/2][W/2][C]
-    const uint8_t* idx;    // winner index per pooled element
-    const float* dskip;    // the concat gradient's skip half (offset applied), row stride ldskip
-    int ldskip;
-    const float *msc, *msh;  // BN -> ReLU mask affine, or null
-    int H, W;              // full-resolution grid
-    float rH, rW;
-};
-// HEAD (r06, option head_fuse on the bf16 path): the last conv's do = [BN -> ReLU: fma(y, sc, sh)
-// > 0] dl[m] w[c], head_bwd's expression bit for bit (one output channel), as
-// kernels_gemm_x3.hip bn_dz_x3_kernel<1>: head_bwd stores no full-resolution f32 do
-struct Dz16Head {
-    const float* dl;       // d logits [P]
-    const float* w;        // head weights [C]
-    const float *sc, *sh;  // the last BN's forward affine
-    int relu;
-};
-template <int SRC>  // 0: do from memory, 1: Dz16Head, 2: Dz16Pool
+// The dz pass writing the dense bf16 image the LDS-DMA dgrad / wgrad read (round to nearest
+// even, as k_to_bf16), and the f32 dz in place only when another consumer still reads it
+// (f32 != 0, stored do only).  8 channels per thread, U rows in flight.
+template <int SRC>  // 0: do from memory, 1: DzHead, 2: DzPool
 __global__ __launch_bounds__(256) void bn_dz16_kernel(float* __restrict__ d, const float* __restrict__ y,
                                                       int ld, int off, int64_t P, int C,
                                                       const float* __restrict__ coef, int mask,
-                                                      int tpr, __bf16* __restrict__ dz16, int f32, Dz16Pool pl,
-                                                      Dz16Head hd) {
+                                                      int tpr, __bf16* __restrict__ dz16, int f32, DzPool pl,
+                                                      DzHead hd) {
     typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-    constexpr bool POOL = SRC == 2, HEAD = SRC == 1;
     constexpr int U = 4;  // rows per thread per trip: 16 independent 16-B loads in flight
     const int rpp = 256 / tpr;
     const int c_first = (threadIdx.x % tpr) * 8;
     for (int64_t m0 = (int64_t)blockIdx.x * rpp * U + threadIdx.x / tpr; m0 < P;
          m0 += (int64_t)gridDim.x * rpp * U) {
         for (int c = c_first; c < C; c += tpr * 8) {
-            // the BN -> ReLU mask affine of this thread's 8 channels, in registers (loaded per
-            // element inside the row loop, the fused pass ran 1.5x slower than the unfused pair)
-            f32x4 msc[2], msh[2], hw[2], hs[2], hh[2];
-            if (POOL && pl.msc) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    msc[h] = *(const f32x4*)(pl.msc + c + 4 * h);
-                    msh[h] = *(const f32x4*)(pl.msh + c + 4 * h);
-                }
-            }
-            if constexpr (HEAD) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    hw[h] = *(const f32x4*)(hd.w + c + 4 * h);
-                    hs[h] = *(const f32x4*)(hd.sc + c + 4 * h);
-                    hh[h] = *(const f32x4*)(hd.sh + c + 4 * h);
-                }
-            }
-            f32x4 dv[U][2], yv[U][2];
-            f32x4 gp[U][2];
-            float dl[U];
-            uint32_t wi[U][2];
-            int kk[U];
+            const DzSrcCoef sk = dz_src_coef<SRC>(hd, pl, c);
+            DzRow r[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t m = m0 + u * rpp;
-                if (m < P) {
-                    int64_t po = 0;
-                    if constexpr (HEAD) dl[u] = hd.dl[m];
-                    if constexpr (POOL) {
-                        const Pix q = decode_fast((int)m, pl.H, pl.W, pl.rH, pl.rW);
-                        po = ((int64_t)q.img * (pl.H >> 1) + (q.y >> 1)) * (pl.W >> 1) + (q.x >> 1);
-                        kk[u] = (q.y & 1) * 2 + (q.x & 1);
-                        const uint2 w2 = *(const uint2*)(pl.idx + po * C + c);
-                        wi[u][0] = w2.x;
-                        wi[u][1] = w2.y;
-                    }
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        if constexpr (POOL) {
-                            dv[u][h] = *(const f32x4*)(pl.dskip + m * pl.ldskip + c + 4 * h);
-                            gp[u][h] = *(const f32x4*)(pl.dp + po * C + c + 4 * h);
-                        } else if constexpr (!HEAD) {
-                            dv[u][h] = *(const f32x4*)(d + m * C + c + 4 * h);
-                        }
-                        yv[u][h] = *(const f32x4*)(y + m * ld + off + c + 4 * h);
-                    }
-                }
+                if (m < P) dz_load<SRC>(r[u], d, y, ld, off, C, m, c, hd, pl);
             }
-            if constexpr (POOL) {
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if (((wi[u][h] >> (8 * j)) & 0xFF) == (uint32_t)kk[u]) dv[u][h][j] += gp[u][h][j];
-                            if (pl.msc && !bn_relu_on(yv[u][h][j], msc[h][j], msh[h][j]))
-                                dv[u][h][j] = 0.f;
-                        }
-            }
-            if constexpr (HEAD) {
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const bool on = !hd.relu || bn_relu_on(yv[u][h][j], hs[h][j], hh[h][j]);
-                            dv[u][h][j] = on ? dl[u] * hw[h][j] : 0.f;
-                        }
-            }
-            f32x4 ka[2], kb[2], kc[2], km[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                ka[h] = *(const f32x4*)(coef + c + 4 * h);
-                kb[h] = *(const f32x4*)(coef + C + c + 4 * h);
-                kc[h] = *(const f32x4*)(coef + 2 * C + c + 4 * h);
-                km[h] = *(const f32x4*)(coef + 3 * C + c + 4 * h);
-            }
+            const DzCoef k = dz_coef(coef, C, c);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t m = m0 + u * rpp;
                 if (m >= P) break;
+                f32x4 o[2];
+                dz_form<SRC>(r[u], k, sk, mask, hd, pl, o);
                 bf16x8 o16;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const f32x4 v = yv[u][h];
-                    const f32x4 r = bn_dz4(ka[h], dv[u][h], kb[h], v, km[h], kc[h]);
-                    f32x4 o;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        o[j] = (!mask || v[j] > 0.f) ? r[j] : 0.f;
-                        o16[4 * h + j] = (__bf16)o[j];
-                    }
-                    if (SRC == 0 && f32) *(f32x4*)(d + m * C + c + 4 * h) = o;
+                    for (int j = 0; j < 4; ++j) o16[4 * h + j] = (__bf16)o[h][j];
+                    if (SRC == 0 && f32) *(f32x4*)(d + m * C + c + 4 * h) = o[h];
                 }
                 *(bf16x8*)(dz16 + m * C + c) = o16;
             }
         }
-    }
-}
-
-__global__ void bn_dz_kernel(float* __restrict__ d, const float* __restrict__ y, int ld, int off,
-                             int64_t P, int C, const float* __restrict__ coef, int mask) {
-    const int c4n = C / 4;
-    const int64_t total = P * c4n;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % c4n) * 4;
-        const int64_t m = i / c4n;
-        f32x4* pd = (f32x4*)(d + m * C + c);
-        const f32x4 v = *(const f32x4*)(y + m * ld + off + c);
-        const f32x4 r = *(const f32x4*)(coef + c) * (*pd) +
-                        *(const f32x4*)(coef + C + c) * (v - *(const f32x4*)(coef + 3 * C + c)) +
-                        *(const f32x4*)(coef + 2 * C + c);
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (!mask || v[j] > 0.f) ? r[j] : 0.f;
-        *pd = o;
     }
 }
 
@@ -1469,7 +1344,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     // two pixels per trip, both pixels' loads issued first (P < 2^31: 32-bit pixel math);
     // each thread still accumulates its pixels in increasing m (same partials)
     auto one = [&](int m, const f32x4& yr, const float (&dl)[4]) {
-        f32x4 v;  // explicit fma: bn_dz_x3's fused head source recomputes this mask (r05)
+        f32x4 v;  // (one output channel: the fused dz passes recompute d below as dz_pass.h dz_head_do)
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = bn_act(yr[j], sc[j], sh[j]);
         if (relu)
@@ -1957,16 +1832,6 @@ int k_bn_bwd_finalize2(const float* part, int G, int C, double count, const floa
                        count, gamma, mean, invstd, coef, dgamma, dbeta);
     LAUNCH_CHECK();
 }
-int k_bn_dz(float* d, const float* y, int ld, int off, int64_t P, int C, const float* coef, int mask,
-            hipStream_t s) {
-    if (C % 4 == 0 && C >= 4 && C <= 1024)
-        hipLaunchKernelGGL(bn_dz_rows_kernel, dim3(grid_for(P * (C / 4))), dim3(256), 0, s, d, y, ld,
-                           off, P, C, coef, mask);
-    else
-        hipLaunchKernelGGL(bn_dz_kernel, dim3(grid_for(P * (C / 4))), dim3(256), 0, s, d, y, ld, off,
-                           P, C, coef, mask);
-    LAUNCH_CHECK();
-}
 int k_to_bf16(const float* src, int ld, int off, int C, const float* scale, const float* shift,
               int relu, int64_t P, uint16_t* dst, hipStream_t s, int dld) {
     if (dld == 0) dld = C;
@@ -1979,35 +1844,47 @@ int k_to_bf16(const float* src, int ld, int off, int C, const float* scale, cons
                        scale, shift, relu, P, tpr, (__bf16*)dst, dld);
     LAUNCH_CHECK();
 }
-int k_bn_dz16(float* d, const float* y, int ld, int off, int64_t P, int C, const float* coef,
-              int mask, uint16_t* dz16, int f32, hipStream_t s, const float* hdl, const float* hw,
-              const float* hsc, const float* hsh, int hrelu) {
-    if (C % 8 || ld % 4 || off % 4) return -1;
-    const int c8 = C / 8;
-    const int tpr = c8 >= 256 ? 256 : c8;
-    if (256 % tpr || (c8 > 256 && c8 % 256)) return -1;
-    if (hdl) {  // do recomputed from the head: no do to read, none to write back
-        if (!hw || !hsc || !hsh || f32) return -1;
-        hipLaunchKernelGGL(bn_dz16_kernel<1>, dim3(grid_for((P + 3) / 4 * tpr)), dim3(256), 0, s, nullptr, y, ld,
-                           off, P, C, coef, mask, tpr, (__bf16*)dz16, 0, Dz16Pool{},
-                           Dz16Head{hdl, hw, hsc, hsh, hrelu});
+int k_bn_dz(const DzArgs& a, hipStream_t s) {
+    const bool head = a.head.dl != nullptr, pool = a.pool.dp != nullptr;
+    if (!a.y || !a.coef || a.P < 1 || a.C < 4 || a.C % 4 || a.ld % 4 || a.off % 4) return -1;
+    if ((a.d != nullptr) + head + pool != 1) return -1;  // exactly one source
+    if ((a.dz16 && a.dz3) || (a.bpart && !a.dz3)) return -1;
+    // f32 in place: over a stored do, alone or beside the bf16 image; else there is an image
+    if (a.f32 ? !a.d || a.dz3 : !(a.dz16 || a.dz3)) return -1;
+    if (head && (!a.head.w || !a.head.sc || !a.head.sh)) return -1;
+    DzPool pl = a.pool;
+    if (pool) {
+        if (!pl.idx || !pl.dskip || pl.ldskip % 4 || pl.H % 2 || pl.W % 2 || (int64_t)a.N * pl.H * pl.W != a.P ||
+            a.P >= (1LL << 24))
+            return -1;
+        pl.rH = 1.f / (float)pl.H;
+        pl.rW = 1.f / (float)pl.W;
+    }
+    if (a.dz3) {
+        if (a.C % 32 || (a.bpart && a.C > 2048)) return -1;
+        DzArgs b = a;
+        b.pool = pl;
+        return k_bn_dz_x3(b, s);
+    }
+    if (!a.dz16) {
+        hipLaunchKernelGGL(bn_dz_rows_kernel, dim3(grid_for(a.P * (a.C / 4))), dim3(256), 0, s, a.d, a.y, a.ld,
+                           a.off, a.P, a.C, a.coef, a.mask);
         LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(bn_dz16_kernel<0>, dim3(grid_for((P + 3) / 4 * tpr)), dim3(256), 0, s, d, y, ld, off,
-                       P, C, coef, mask, tpr, (__bf16*)dz16, f32, Dz16Pool{}, Dz16Head{});
-    LAUNCH_CHECK();
-}
-int k_bn_dz16_pool(const float* y, int ld, int off, int64_t P, int C, const float* coef, int mask,
-                   uint16_t* dz16, const float* dp, const uint8_t* idx, const float* dskip, int ldskip,
-                   const float* msc, const float* msh, int N, int H, int W, hipStream_t s) {
-    if (C % 8 || ld % 4 || off % 4 || ldskip % 4) return -1;
-    if (!dp || !idx || !dskip || H % 2 || W % 2 || (int64_t)N * H * W != P || P >= (1LL << 24)) return -1;
-    const int c8 = C / 8;
+    const int c8 = a.C / 8;
     const int tpr = c8 >= 256 ? 256 : c8;
-    if (256 % tpr || (c8 > 256 && c8 % 256)) return -1;
-    const Dz16Pool pl{dp, idx, dskip, ldskip, msc, msh, H, W, 1.f / (float)H, 1.f / (float)W};
-    hipLaunchKernelGGL(bn_dz16_kernel<2>, dim3(grid_for((P + 3) / 4 * tpr)), dim3(256), 0, s, nullptr, y, ld,
-                       off, P, C, coef, mask, tpr, (__bf16*)dz16, 0, pl, Dz16Head{});
+    if (a.C % 8 || 256 % tpr || (c8 > 256 && c8 % 256)) return -1;
+    const dim3 grid(grid_for((a.P + 3) / 4 * tpr));
+#define DZ16(SRC)                                                                                            \
+    hipLaunchKernelGGL(bn_dz16_kernel<SRC>, grid, dim3(256), 0, s, a.d, a.y, a.ld, a.off, a.P, a.C, a.coef, \
+                       a.mask, tpr, (__bf16*)a.dz16, a.f32 ? 1 : 0, pl, a.head)
+    if (head)
+        DZ16(1);
+    else if (pool)
+        DZ16(2);
+    else
+        DZ16(0);
+#undef DZ16
     LAUNCH_CHECK();
 }
 int k_bias_reduce(const float* slab, int S, int taps, int C, float* out, hipStream_t s) {

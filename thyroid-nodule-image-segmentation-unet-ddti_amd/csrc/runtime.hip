@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "dz_pass.h"
 #include "runtime_internal.h"
 
 namespace {
@@ -1583,14 +1584,8 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
     // inside the weight gradient's B' loader, which also stores it for the dgrad
     const int dz_mask = c->bn_relu ? 0 : 1;
     // what the dz pass of an encoder block's second conv recomputes its `do` from where the
-    // route says pool_fuse (r05): the max-pool backward's inputs
-    struct PoolSrc {
-        const float* dp = nullptr;
-        const uint8_t* idx = nullptr;
-        const float* dskip = nullptr;
-        int ldskip = 0;
-        const float *msc = nullptr, *msh = nullptr;
-    } pool_src;
+    // route says pool_fuse: the max-pool backward's inputs (the encoder loop fills it)
+    DzPool pool_src;
     // conv i backward from do_i (dense [P][cout]).
     // dgrad -> dx (ld ldx).  bn_next: dx is the `do` of BN layer i-1 (second conv of a
     // block), so the epilogue also emits that layer's partials; *rows = their count.
@@ -1616,26 +1611,43 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         w.bmode = G_IDENT;
         w.Mw = 9 * C.cin;
         w.Nw = C.cout;
-        bool dzw = false;
         int t16 = -1;
-        if (rt.wgrad == FAM_X3) {
-            // option x3: dz as an x3 image (and the conv bias's column partials), the weight
-            // gradient from the forward's kept input image and dz, the input gradient from dz
-            float* bp = C.b >= 0 ? p.part : nullptr;
-            if (rt.pool_fuse) {  // (r05) do straight from the max-pool backward's inputs
-                const PoolSrc& q = pool_src;
-                RUN("bn_dz", 0, k_bn_dz_x3_pool(p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask, p.s3,
-                                                bp, q.dp, q.idx, q.dskip, q.ldskip, q.msc, q.msh, p.N, Hl,
-                                                Wl, s));
+        // the dz pass (dz_pass.h).  Outputs by family: x3 -> the x3 image (and the conv bias's
+        // column partials); LDS-DMA dgrad / wgrad -> the bf16 image, with the f32 dz in place
+        // only while a register-staged kernel still consumes it; else f32 in place
+        const bool x3 = rt.wgrad == FAM_X3;
+        const bool wg16 = !x3 && rt.wgrad == FAM_DMA16, rg16 = !x3 && rt.dgrad == FAM_DMA16;
+        const bool dz16 = rg16 || wg16;
+        const bool f32 = !x3 && (!wg16 || !(dx && rg16));
+        // option dz_in_wgrad: the weight gradient's B' loader forms dz from do and y (the
+        // bn_dz pass disappears) and its first A'-tile blocks store it for the dgrad; f32
+        // register-staged weight-gradient tiles only, with a dgrad to feed (both BN orders;
+        // BN -> ReLU forms dz unmasked, do already carries the ReLU mask)
+        const bool dzw = !x3 && p.gdz && C.cin <= c->opt.dz_in_wgrad && !dz16 && dx && (wc.tile < 10 || wc.tile >= 20);
+        if (!dzw) {
+            DzArgs z;
+            z.y = p.y[i], z.ld = p.ldy[i], z.off = p.offy[i];
+            z.P = P, z.C = C.cout, z.coef = p.coef, z.mask = dz_mask;
+            // the image outputs can take a do that its producer did not store
+            if (rt.pool_fuse && (x3 || dz16)) {
+                if (f32) return fail(c, UNET_ERR_INTERNAL, "pool_fuse: conv %d needs an f32 dz", i);
+                z.pool = pool_src;
+                z.pool.H = Hl, z.pool.W = Wl, z.N = p.N;
+            } else if (rt.head_fuse && (x3 || dz16)) {
+                if (f32) return fail(c, UNET_ERR_INTERNAL, "head_fuse: conv %d needs an f32 dz", i);
+                z.head = DzHead{dlogits, prm + c->head_w, p.scale[i], p.shift[i], c->bn_relu ? 1 : 0};
             } else {
-                // (r05) head_fuse: the last conv's `do` straight from the 1x1 head (head_bwd stored none)
-                const bool hsrc = rt.head_fuse;
-                RUN("bn_dz", 0, k_bn_dz_x3(dout, p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask,
-                                          p.s3, bp, s, hsrc ? dlogits : nullptr,
-                                          hsrc ? prm + c->head_w : nullptr, hsrc ? p.scale[i] : nullptr,
-                                          hsrc ? p.shift[i] : nullptr, c->bn_relu ? 1 : 0));
+                z.d = const_cast<float*>(dout);
             }
-            if (bp) {  // many 256-row partials: one two-level reduction (as the BN statistics)
+            z.f32 = f32;
+            z.dz16 = dz16 ? p.s16 : nullptr;
+            z.dz3 = x3 ? p.s3 : nullptr;
+            z.bpart = x3 && C.b >= 0 ? p.part : nullptr;
+            RUN("bn_dz", 0, k_bn_dz(z, s));
+        }
+        if (x3) {
+            // the weight gradient from the forward's kept input image and dz, the input gradient from dz
+            if (C.b >= 0) {  // many 256-row partials: one two-level reduction (as the BN statistics)
                 const int G = x3_dz_blocks(P);
                 if (G > STAT_G) {
                     RUN("bias_grad", 0, k_reduce_rows(p.part, G, C.cout, p.part2, STAT_G, s));
@@ -1646,37 +1658,6 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
             }
             use_images(c, p, w, FAM_X3, p.x3[i]);
         } else {
-            // bf16 image of dz: A operand of the LDS-DMA dgrad, B' of the LDS-DMA wgrad; the f32
-            // dz is still written when the register-staged kernel of either consumes it
-            const bool wg16 = rt.wgrad == FAM_DMA16, rg16 = rt.dgrad == FAM_DMA16;
-            const bool dz16 = rg16 || wg16;
-            // option dz_in_wgrad: the weight gradient's B' loader forms dz from do and y (the
-            // bn_dz pass disappears) and its first A'-tile blocks store it for the dgrad; f32
-            // register-staged weight-gradient tiles only, with a dgrad to feed (r04: both BN orders;
-            // BN -> ReLU forms dz unmasked, do already carries the ReLU mask)
-            dzw = p.gdz && C.cin <= c->opt.dz_in_wgrad && !dz16 && dx && (wc.tile < 10 || wc.tile >= 20);
-            if (dzw) {
-            } else if (dz16) {
-                const bool f32 = !wg16 || !(dx && rg16);
-                if (rt.pool_fuse && !f32) {  // (r06) do straight from the max-pool backward's inputs
-                    const PoolSrc& q = pool_src;
-                    RUN("bn_dz", 0, k_bn_dz16_pool(p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask, p.s16,
-                                                   q.dp, q.idx, q.dskip, q.ldskip, q.msc, q.msh, p.N, Hl, Wl, s));
-                } else if (rt.pool_fuse) {
-                    return fail(c, UNET_ERR_INTERNAL, "pool_fuse: conv %d needs an f32 dz", i);
-                } else if (rt.head_fuse) {  // (r06) do straight from the 1x1 head
-                    if (f32) return fail(c, UNET_ERR_INTERNAL, "head_fuse: conv %d needs an f32 dz", i);
-                    RUN("bn_dz", 0, k_bn_dz16(nullptr, p.y[i], p.ldy[i], p.offy[i], P, C.cout, p.coef, dz_mask,
-                                              p.s16, 0, s, dlogits, prm + c->head_w, p.scale[i], p.shift[i],
-                                              c->bn_relu ? 1 : 0));
-                } else {
-                    RUN("bn_dz", 0, k_bn_dz16(const_cast<float*>(dout), p.y[i], p.ldy[i], p.offy[i], P, C.cout,
-                                              p.coef, dz_mask, p.s16, f32 ? 1 : 0, s));
-                }
-            } else {
-                RUN("bn_dz", 0, k_bn_dz(const_cast<float*>(dout), p.y[i], p.ldy[i], p.offy[i], P, C.cout,
-                                        p.coef, dz_mask, s));
-            }
             w.xcd = xcd_remap_wgrad(c);
             set_operand(w, conv_input(c, p, i));
             w.b = dout;
@@ -1929,7 +1910,7 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         // rows fit: p.part holds P/64 + 1 rows of 2C for every conv of the level
         const int Gmp = wide_g(p.P[b]);
         const bool pool_fuse = p.rt.conv[i1].pool_fuse;
-        pool_src = PoolSrc{};
+        pool_src = DzPool{};
         if (pool_fuse) {
             pool_src.dp = cur;
             pool_src.idx = p.idx[b];
