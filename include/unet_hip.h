@@ -26,6 +26,9 @@
  *                                                           distance_transform_edt(1 - gt), on the
  *                                                           device (no host round trip)
  *   unet_boundary_fwd / _bwd        models/loss.py:52-66   BoundaryLoss and its d/d(logits)
+ *   unet_lovasz_fwd / _bwd / _host  (new)                  Lovasz hinge loss (the convex surrogate of
+ *                                                           the Jaccard index) over a stable segmented
+ *                                                           radix sort, and its d/d(logits)
  *   unet_surface_stats / _host      (new)                  per-sample surface-distance statistics
  *                                                           of Trainer.test's masks (HD, HD95,
  *                                                           ASSD: MedPy's hd / hd95 / assd)
@@ -237,6 +240,38 @@ int unet_boundary_fwd(unet_ctx* ctx, const float* logits, const float* targets, 
 int unet_boundary_bwd(unet_ctx* ctx, const float* logits, const float* targets, const float* dist,
                       int N, int C, int H, int W, const float* w, float* dlogits,
                       unet_stream_t stream);
+
+/* Lovasz hinge loss (Berman et al., CVPR 2018, per_image=True; rules in csrc/lovasz.h, kernels in
+ * csrc/kernels_lovasz.hip).  Every (n, c) plane of logits / targets (N, C, H, W) is its own binary
+ * problem over its M = H W pixels, i the raster index:
+ *   label   y_i = (t_i >= 0.5f), s_i = y_i ? +1 : -1: a soft (mixup) target is binarised at one half;
+ *   error   e_i = fl32(1 - s_i x_i) (the product is exact: one rounding);
+ *   order   descending e, ties by ascending i (a STABLE sort: np.argsort(-e, kind="stable")); +0 and
+ *           -0 are equal keys, +-inf sort as values; the place of a NaN is unspecified, its plane's
+ *           loss is NaN, and no index ever leaves the plane;
+ *   counts  P = sum y; cTP_r, cFP_r = positives / negatives among the ranks <= r (exact integers);
+ *   weights J_r = 1 - (P - cTP_r) / (P + cFP_r) in float64 (the denominator is >= 1), J_{-1} = 0,
+ *           g_r = J_r - J_{r-1};
+ *   loss    L_plane = sum_r max(e_r, 0) g_r, products and sum in float64 in a fixed order (run-to-run
+ *           deterministic).
+ *   unet_lovasz_fwd  gmap (N, C, H, W) f32, in PIXEL order: fl32(g_rank(i)) where e_i > 0, 0 elsewhere
+ *                  (the per-pixel weight the backward needs); perm (optional, may be null): uint32
+ *                  (N, C, H W), the raster indices of every plane in sorted order, all M of them;
+ *                  sum (device fp64[1]) = sum_planes L_plane; loss (device fp32[1]) = sum / (N C).
+ *                  H W > 2^24 is UNET_ERR_SHAPE; no other shape constraint.
+ *   unet_lovasz_bwd  dlogits_i = (w[0] * -s_i) * gmap_i / (N C) where e_i > 0, 0 elsewhere
+ *                  (relu'(0) = 0), in float32 in this order; w a device fp32[1].
+ *   unet_lovasz_host HOST function: the same rules (csrc/lovasz.h, shared host / device source) with a
+ *                  stable sort by key, on host pointers; gmap and perm are bit-equal to the device's.
+ * All work is enqueued on `stream` with no host synchronisation; the scratch (16 bytes per pixel) is
+ * owned by the context and grown on demand (an outgrown buffer is released by unet_destroy), so issue
+ * a context's Lovasz calls on one stream, or order the streams. */
+int unet_lovasz_fwd(unet_ctx* ctx, const float* logits, const float* targets, int N, int C, int H, int W,
+                    float* gmap, uint32_t* perm, double* sum, float* loss, unet_stream_t stream);
+int unet_lovasz_bwd(unet_ctx* ctx, const float* logits, const float* targets, const float* gmap, int N,
+                    int C, int H, int W, const float* w, float* dlogits, unet_stream_t stream);
+int unet_lovasz_host(const float* logits, const float* targets, int N, int C, int H, int W, float* gmap,
+                     uint32_t* perm, double* sum, float* loss);
 
 /* AdamW over flat arenas of n floats (one launch for all parameter tensors; any part of a
  * parameter arena, too: the weight images of unet_adamw_repack are dropped if it overlaps theirs).

@@ -224,6 +224,18 @@ int k_curve_hist(const float* x, const float* t, int planes, int64_t hw, const f
 int k_curve_stats(const int32_t* plane_hist, int planes, int B, void* scratch, int64_t* out_i64,
                   double* dice_sum, hipStream_t s);
 
+// Lovasz hinge loss (kernels_lovasz.hip; rules in lovasz.h): the segmented stable radix sort of every
+// plane's errors, the loss and the per-pixel weights gmap (perm may be null), and the dlogits pass.
+// scratch holds lovasz_scratch_bytes(N, C, H, W).  The callers have checked the arguments.
+bool lovasz_shape_ok(int N, int C, int H, int W);
+size_t lovasz_scratch_bytes(int N, int C, int H, int W);
+int k_lovasz_fwd(const float* x, const float* t, int N, int C, int H, int W, void* scratch, float* gmap,
+                 uint32_t* perm, double* sum, float* loss, hipStream_t s);
+int k_lovasz_bwd(const float* x, const float* t, const float* gmap, int N, int C, int H, int W, const float* w,
+                 float* dx, hipStream_t s);
+void lovasz_host(const float* x, const float* t, int N, int C, int H, int W, float* gmap, uint32_t* perm,
+                 double* sum, float* loss);
+
 // Predict-mode export (kernels_export.hip; rules and the host twins in export.h): the float32
 // resize of one plane fused with the threshold (plane may be null; scratch holds
 // export_scratch_bytes(h, w, ow)) and the contour / tint overlay with the mask statistics (gt may

@@ -1,5 +1,5 @@
 // The stand-alone entry points of include/unet_hip.h: losses, distance transform, surface and
-// lesion metrics, connected components, test-time augmentation, the threshold sweep, the predict-mode
+// lesion metrics, the Lovasz hinge loss, connected components, test-time augmentation, the threshold sweep, the predict-mode
 // export (resize back + overlay), resize and the training augmentations, each with its host twin where
 // it has one.  None of them reads the layer graph
 // or a workspace plan (runtime.hip): they use the context's device, error string, launch timer
@@ -148,6 +148,38 @@ int unet_boundary_bwd(unet_ctx* c, const float* logits, const float* targets, co
     return launched(c, "boundary_bwd",
                     k_boundary_bwd(logits, targets, dist, N, C, (int64_t)H * W, w, dlogits, (hipStream_t)stream));
     ABI_CATCH(c)
+}
+
+// ---- Lovasz hinge loss (kernels_lovasz.hip, lovasz.h) ----
+int unet_lovasz_fwd(unet_ctx* c, const float* logits, const float* targets, int N, int C, int H, int W,
+                    float* gmap, uint32_t* perm, double* sum, float* loss, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !logits || !targets || !gmap || !sum || !loss) return UNET_ERR_INVALID;
+    if (!lovasz_shape_ok(N, C, H, W))
+        return fail(c, UNET_ERR_SHAPE, "lovasz: N, C, H, W >= 1 and H * W <= 2^24");
+    if (int r = grow(c, c->lovasz, lovasz_scratch_bytes(N, C, H, W), "lovasz")) return r;
+    return launched(c, "lovasz_fwd",
+                    k_lovasz_fwd(logits, targets, N, C, H, W, c->lovasz.p, gmap, perm, sum, loss,
+                                 (hipStream_t)stream));
+    ABI_CATCH(c)
+}
+
+int unet_lovasz_bwd(unet_ctx* c, const float* logits, const float* targets, const float* gmap, int N, int C,
+                    int H, int W, const float* w, float* dlogits, unet_stream_t stream) {
+    ABI_TRY
+    if (!c || !logits || !targets || !gmap || !w || !dlogits) return UNET_ERR_INVALID;
+    if (!lovasz_shape_ok(N, C, H, W))
+        return fail(c, UNET_ERR_SHAPE, "lovasz: N, C, H, W >= 1 and H * W <= 2^24");
+    return launched(c, "lovasz_bwd",
+                    k_lovasz_bwd(logits, targets, gmap, N, C, H, W, w, dlogits, (hipStream_t)stream));
+    ABI_CATCH(c)
+}
+
+int unet_lovasz_host(const float* logits, const float* targets, int N, int C, int H, int W, float* gmap,
+                     uint32_t* perm, double* sum, float* loss) {
+    if (!logits || !targets || !gmap || !sum || !loss) return UNET_ERR_INVALID;
+    if (!lovasz_shape_ok(N, C, H, W)) return UNET_ERR_SHAPE;
+    return catch_to_status([&] { lovasz_host(logits, targets, N, C, H, W, gmap, perm, sum, loss); });
 }
 
 static bool surf_shape_ok(int N, int C, int H, int W) {

@@ -2042,7 +2042,8 @@ int unet_destroy(unet_ctx* c) {
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     // (a retired buffer implies a live scratch; nothing allocated: no device call at all)
     void* const own[] = {c->pp,      c->pp3,       c->loss.p,    c->boundary.p, c->clahe.p,
-                         c->elastic.p, c->surface.p, c->cc.p,    c->curve.p,   c->exportbuf.p};
+                         c->elastic.p, c->surface.p, c->cc.p,    c->curve.p,   c->exportbuf.p,
+                         c->lovasz.p};
     if (std::any_of(std::begin(own), std::end(own), [](void* p) { return p != nullptr; })) {
         (void)hipSetDevice(c->device);
         for (void* p : own)

@@ -244,6 +244,7 @@ struct unet_ctx {
     Scratch cc;        // unet_components / _postprocess / _lesion_stats: labels, areas and flags, counts
     Scratch curve;     // unet_curve_stats: the planes' dice_k before their ordered sum
     Scratch exportbuf; // unet_resize_f32_mask: the float32 intermediate of the horizontal pass
+    Scratch lovasz;    // unet_lovasz_fwd: the sort's key / word buffers, histograms, tile sums
     std::vector<void*> retired;
 
     int nconv() const { return (int)conv.size(); }

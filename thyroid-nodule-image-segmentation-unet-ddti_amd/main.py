@@ -94,6 +94,8 @@ def get_parser(argv=None):
     p.add_argument("--dice_ratio", type=float, default=0)
     p.add_argument("--focal_ratio", type=float, default=1)
     p.add_argument("--boundary_ratio", type=float, default=0)
+    p.add_argument("--lovasz_ratio", type=float, default=0,
+                   help="weight of the Lovasz hinge loss (the Jaccard surrogate), sorted on the GPU; 0: off")
     p.add_argument("--num_workers", default=4, type=int)
     p.add_argument("--epochs", type=int, default=10000)
     p.add_argument("--batch_size", default=16, type=int)

@@ -12,13 +12,17 @@ the logits, and each module below just picks its term:
 target.  On GPU tensors it runs on the device (``unet_hip.boundary_loss``: an exact distance
 transform in HIP, bit-equal to scipy's, one loss and one dlogits kernel, no host sync); CPU
 tensors keep the reference's scipy + torch path.
+
+``LovaszHingeLoss`` is not in the reference: the Lovasz hinge (Berman et al., CVPR 2018), the convex
+surrogate of the Jaccard index the trainer selects checkpoints on, per (sample, channel) plane
+(``unet_hip.lovasz_hinge``: a stable segmented radix sort in HIP, one dlogits kernel, no host sync).
 """
 import numpy as np
 import scipy.ndimage as nd
 import torch
 import torch.nn as nn
 
-from unet_hip import boundary_loss, distance_maps, seg_losses
+from unet_hip import boundary_loss, distance_maps, lovasz_hinge, seg_losses
 
 
 class BCEWithLogitsLoss(nn.Module):
@@ -74,13 +78,21 @@ class BoundaryLoss(nn.Module):
         return per.mean()
 
 
-class CompositeLoss(nn.Module):
-    """λ_ft·FocalTversky(0.3, 0.7, 0.75) + λ_b·Boundary [+ λ_bce·BCE + λ_dice·Dice]
-    (reference models/loss.py:68-82)."""
+class LovaszHingeLoss(nn.Module):
+    """Lovasz hinge loss, the mean over the (sample, channel) planes (Berman's per_image=True);
+    soft targets are binarised at 0.5.  HIP path only, like the fused losses."""
 
-    def __init__(self, λ_ft=1.0, λ_b=0.5, λ_bce=0.0, λ_dice=0.0):
+    def forward(self, logits, targets):
+        return lovasz_hinge(logits, targets)
+
+
+class CompositeLoss(nn.Module):
+    """λ_ft·FocalTversky(0.3, 0.7, 0.75) + λ_b·Boundary [+ λ_bce·BCE + λ_dice·Dice + λ_lovasz·Lovasz]
+    (reference models/loss.py:68-82; the Lovasz term is this project's, off by default)."""
+
+    def __init__(self, λ_ft=1.0, λ_b=0.5, λ_bce=0.0, λ_dice=0.0, λ_lovasz=0.0):
         super().__init__()
-        self.λ_ft, self.λ_b, self.λ_bce, self.λ_dice = λ_ft, λ_b, λ_bce, λ_dice
+        self.λ_ft, self.λ_b, self.λ_bce, self.λ_dice, self.λ_lovasz = λ_ft, λ_b, λ_bce, λ_dice, λ_lovasz
         self.bl = BoundaryLoss()
 
     def forward(self, logits, targets):
@@ -90,4 +102,6 @@ class CompositeLoss(nn.Module):
             loss = loss + self.λ_bce * l[0]
         if self.λ_dice > 0:
             loss = loss + self.λ_dice * l[1]
+        if self.λ_lovasz > 0:
+            loss = loss + self.λ_lovasz * lovasz_hinge(logits, targets)
         return loss

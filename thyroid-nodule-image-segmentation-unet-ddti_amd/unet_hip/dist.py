@@ -170,8 +170,8 @@ class DistributedUNet:
     def empty_step(self, extra_scalar_reduces=0):
         """This rank's shard of the batch is empty (a last batch with fewer samples than
         ranks, data.data_loader.DataParallelShardSampler): join the step's collectives -- the
-        loss sums, `extra_scalar_reduces` single-value all-reduces (the trainer's boundary
-        loss), the gradient buckets -- with zero contributions, so that every rank then
+        loss sums, `extra_scalar_reduces` single-value all-reduces (the trainer's sample count and
+        its boundary / Lovasz losses), the gradient buckets -- with zero contributions, so that every rank then
         applies the same summed gradients."""
         st = self.model.flatten_()
         dev = st.param_arena.device

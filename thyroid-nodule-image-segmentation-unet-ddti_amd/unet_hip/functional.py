@@ -14,6 +14,9 @@
 * ``BoundaryLossFunction`` - BoundaryLoss (models/loss.py:48-66) over a distance map computed
   on the device (``distance_maps``: the exact Euclidean distance transform kernels); its
   backward is one dlogits kernel weighted by the incoming gradient, again with no host sync.
+* ``LovaszHingeFunction`` - the Lovasz hinge loss over a stable segmented radix sort of every
+  plane's margin errors on the device (``lovasz_hinge``); the forward saves the per-pixel weights
+  ``gmap`` and the backward is one dlogits kernel over them, with no host sync.
 """
 import functools
 
@@ -140,6 +143,67 @@ def boundary_loss(logits, targets, dist=None):
                              f"{tuple(dist.shape)} on {dist.device}")
         dist = dist.detach().contiguous().float()
     return BoundaryLossFunction.apply(logits, targets, dist, rt)
+
+
+class LovaszHingeFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, rt):
+        logits = logits.contiguous()
+        loss, gmap, _, _ = rt.lovasz_fwd(logits, targets)
+        ctx.save_for_backward(logits, targets, gmap)
+        ctx.rt = rt
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, targets, gmap = ctx.saved_tensors
+        w = g.contiguous().float().reshape(1)
+        return ctx.rt.lovasz_bwd(logits, targets, gmap, w), None, None
+
+
+def _lovasz_args(logits, targets):
+    if logits.dim() != 4 or targets.shape != logits.shape:
+        raise ValueError(f"logits / targets must be equal (N, C, H, W), got {tuple(logits.shape)} / "
+                         f"{tuple(targets.shape)}")
+    return targets.detach().contiguous().float()
+
+
+def lovasz_hinge(logits, targets):
+    """The Lovasz hinge loss (Berman et al., CVPR 2018, ``per_image=True``) on the HIP path and the
+    current stream, no host synchronisation: the mean over the (n, c) planes of
+    sum_r max(e_r, 0) g_r, e = 1 - s x sorted descending (ties by raster index: a stable radix sort
+    on the device) and g the increments of the Jaccard loss along the sorted order.  Soft targets
+    are binarised at 0.5 (``t >= 0.5`` is positive).  H W <= 2^24."""
+    rt = _boundary_runtime(logits, "lovasz_hinge")
+    targets = _lovasz_args(logits, targets)
+    return LovaszHingeFunction.apply(logits.float(), targets, rt)
+
+
+def lovasz_hinge_parts(logits, targets, want_perm=False):
+    """What ``unet_lovasz_fwd`` writes, without autograd: a dict of ``loss`` (0-dim float32),
+    ``gmap`` (N, C, H, W) float32 (the per-pixel weight g_rank(i), 0 where e_i <= 0), ``sum``
+    (float64[1], the planes' losses added up) and ``perm`` (int32 (N, C, H W): every plane's raster
+    indices in sorted order; None unless wanted)."""
+    rt = _boundary_runtime(logits, "lovasz_hinge_parts")
+    targets = _lovasz_args(logits, targets)
+    loss, gmap, s, perm = rt.lovasz_fwd(logits.detach().contiguous().float(), targets, want_perm)
+    return dict(loss=loss, gmap=gmap, sum=s, perm=perm)
+
+
+def lovasz_hinge_host(logits, targets, want_perm=False):
+    """``lovasz_hinge_parts`` of CPU tensors through the library's host twin (unet_lovasz_host: the
+    device kernels' rules with a stable sort by key)."""
+    _cc_cpu(logits, "lovasz_hinge_host")
+    _cc_cpu(targets, "lovasz_hinge_host")
+    t = _lovasz_args(logits, targets)
+    x = logits.detach().contiguous().float()
+    N, C, H, W = x.shape
+    gmap = torch.empty_like(x)
+    perm = torch.empty((N, C, H * W), dtype=torch.int32) if want_perm else None
+    s = torch.empty(1, dtype=torch.float64)
+    loss = torch.empty((), dtype=torch.float32)
+    _cc_host_call("unet_lovasz_host", x, t, N, C, H, W, gmap, perm, s, loss)
+    return dict(loss=loss, gmap=gmap, sum=s, perm=perm)
 
 
 SURFACE_FIELDS = ("defined", "n_pg", "n_gp", "max_d2", "d2_lo", "d2_hi")

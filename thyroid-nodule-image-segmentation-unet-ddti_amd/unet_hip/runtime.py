@@ -159,6 +159,28 @@ class UNetRuntime:
         _lib.check(rc, self.ctx, "unet_boundary_bwd")
         return d
 
+    def lovasz_fwd(self, logits, targets, want_perm=False):
+        """Lovasz hinge loss (0-dim fp32), gmap (N, C, H, W) fp32, the batch sum fp64[1] and, when
+        wanted, perm int32 (N, C, H W) of logits / targets (unet_lovasz_fwd)."""
+        N, C, H, W = logits.shape
+        gmap = torch.empty_like(logits)
+        perm = torch.empty((N, C, H * W), dtype=torch.int32, device=logits.device) if want_perm else None
+        s = torch.empty(1, dtype=torch.float64, device=logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        rc = self.lib.unet_lovasz_fwd(self.ctx, _lib.ptr(logits), _lib.ptr(targets), N, C, H, W,
+                                      _lib.ptr(gmap), _lib.ptr(perm), _lib.ptr(s), _lib.ptr(loss),
+                                      _lib.stream_ptr(logits.device))
+        _lib.check(rc, self.ctx, "unet_lovasz_fwd")
+        return loss, gmap, s, perm
+
+    def lovasz_bwd(self, logits, targets, gmap, w):
+        N, C, H, W = logits.shape
+        d = torch.empty_like(logits)
+        rc = self.lib.unet_lovasz_bwd(self.ctx, _lib.ptr(logits), _lib.ptr(targets), _lib.ptr(gmap),
+                                      N, C, H, W, _lib.ptr(w), _lib.ptr(d), _lib.stream_ptr(logits.device))
+        _lib.check(rc, self.ctx, "unet_lovasz_bwd")
+        return d
+
     def adamw(self, params, grads, m, v, step, lr, beta1, beta2, eps, wd, grad_scale=1.0):
         rc = self.lib.unet_adamw(self.ctx, _lib.ptr(params), _lib.ptr(grads), _lib.ptr(m), _lib.ptr(v),
                                  params.numel(), step, float(lr), float(beta1), float(beta2),

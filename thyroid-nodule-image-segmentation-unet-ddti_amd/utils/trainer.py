@@ -26,6 +26,11 @@ What runs where (MI355X-first):
   loss and dlogits kernels, no host sync) and is only evaluated when its ratio != 0 (the
   reference evaluates it every step even at ratio 0; 0 * finite == 0, so skipping it changes
   no number).
+* ``config.lovasz_ratio`` != 0 adds the Lovasz hinge loss (``unet_hip.lovasz_hinge``: a stable segmented
+  radix sort of every plane's margin errors, loss and dlogits kernels, no host sync), a sixth meter,
+  ``Lovasz Loss`` in the loss line and a ``Lovasz Loss/{Train,Validate}`` scalar.  The loss is a mean
+  over planes, so under data parallelism it is handled like the boundary term.  At ratio 0 (the
+  default) nothing of it runs and no line, meter, scalar or collective changes.
 * ``test()`` with ``config.surface_metrics``: HD95, HD and ASSD of every test sample on the
   device too (``unet_hip.surface_metrics``); five sums come back once, at the end.
 * ``test()`` with a ``config.pp_*`` option (``pp_largest``, ``pp_min_area``, ``pp_fill_holes``,
@@ -62,7 +67,7 @@ import torch.distributed as dist
 from torch.optim.lr_scheduler import CosineAnnealingWarmRestarts
 
 import unet_hip
-from models.loss import BoundaryLoss
+from models.loss import BoundaryLoss, LovaszHingeLoss
 from unet_hip.dist import DistributedUNet
 from utils.utils import AverageMeter, EarlyStopping, global_metrics_from_counts, metrics_from_counts
 
@@ -138,6 +143,9 @@ class Trainer:
         self.scheduler = CosineAnnealingWarmRestarts(self.optimizer, T_0=20, T_mult=2, eta_min=0)
         self.focal_abg = (0.4, 0.6, 2.0)  # FocalTverskyLoss() defaults (utils/trainer.py:38)
         self.criterion_boundary = BoundaryLoss()
+        self.lovasz_ratio = float(getattr(config, "lovasz_ratio", 0) or 0)
+        self.criterion_lovasz = LovaszHingeLoss()
+        self._lovasz = None  # the last step's Lovasz loss (the gathered batch's), ratio != 0 only
         self.early_stopping = EarlyStopping(logger=self.logger,
                                             patience=getattr(config, "early_stop_patience", 50), delta=0)
         self.writer = (SummaryWriter(log_dir=getattr(config, "result_dir", None)) if self.rank0
@@ -159,22 +167,40 @@ class Trainer:
         loss = (w * l).sum()
         lb = torch.zeros((), device=logits.device)
         total = loss
-        if c.boundary_ratio != 0:
-            lb = self.criterion_boundary(logits, masks)  # mean over this rank's samples
+        # the per-sample / per-plane means: (ratio, criterion) of the boundary and the Lovasz term
+        extra = [(c.boundary_ratio, self.criterion_boundary), (self.lovasz_ratio, self.criterion_lovasz)]
+        vals = [None, None]
+        frac = None
+        for k, (ratio, crit) in enumerate(extra):
+            if ratio == 0:
+                continue
+            v = crit(logits, masks)  # mean over this rank's samples
             if self.ddp is not None:
                 # gathered-batch mean (models/loss.py:66 divides by the full batch): weight
                 # the local mean by n_local / n_global; gradients are summed over ranks
-                n = torch.tensor([float(logits.shape[0])], device=logits.device)
-                dist.all_reduce(n)
-                lb = lb * (logits.shape[0] / float(n.item()))
-                loss = loss + c.boundary_ratio * lb
-                lb = lb.detach().clone()
-                dist.all_reduce(lb)
-                total = total.detach() + c.boundary_ratio * lb
+                if frac is None:
+                    n = torch.tensor([float(logits.shape[0])], device=logits.device)
+                    dist.all_reduce(n)
+                    frac = logits.shape[0] / float(n.item())
+                v = v * frac
+                loss = loss + ratio * v
+                v = v.detach().clone()
+                dist.all_reduce(v)
+                total = total.detach() + ratio * v
             else:
-                loss = loss + c.boundary_ratio * lb
+                loss = loss + ratio * v
                 total = loss
+            vals[k] = v
+        if vals[0] is not None:
+            lb = vals[0]
+        self._lovasz = vals[1]
         return loss, l, lb, total
+
+    def _extra_reduces(self):
+        """Single-value all-reduces of a step beside the loss sums (what an empty shard joins):
+        the sample count once, then one value per per-sample term that is switched on."""
+        k = (self.config.boundary_ratio != 0) + (self.lovasz_ratio != 0)
+        return k + 1 if k else 0
 
     def _rank0_mixup(self, mix, lam):
         d = torch.tensor([1.0 if mix else 0.0, lam if mix else 0.0], dtype=torch.float64,
@@ -199,10 +225,11 @@ class Trainer:
 
     def _log_epoch(self, tag, epoch, meters, counts):
         acc, precision, recall, f1, iou = metrics_from_counts(counts.tolist())
-        bce, dice, focal, bnd, tot = (m.avg for m in meters)
+        bce, dice, focal, bnd, tot = (m.avg for m in meters[:5])
         self.logger.info(f"{tag} Epoch: {epoch + 1}, Avg Loss: {tot:.4f}")
+        lov = f", Lovasz Loss: {meters[5].avg:.4f}" if len(meters) > 5 else ""
         self.logger.info(f"BCE Loss: {bce:.4f}, Dice Loss: {dice:.4f}, Focal Loss: {focal:.4f}, "
-                         f"Boundary Loss: {bnd:.4f}")
+                         f"Boundary Loss: {bnd:.4f}{lov}")
         self.logger.info(f"acc: {acc:.4f}, precision: {precision:.4f}, recall: {recall:.4f}, "
                          f"f1: {f1:.4f}, IoU: {iou:.4f}")
         name = "Train" if tag == "Train" else "Validate"
@@ -210,18 +237,21 @@ class Trainer:
                      ("Boundary Loss", bnd), ("Acc", acc), ("Precision", precision),
                      ("Recall", recall), ("F1", f1), ("IoU", iou)):
             self.writer.add_scalar(f"{k}/{name}", v, epoch)
+        if len(meters) > 5:
+            self.writer.add_scalar(f"Lovasz Loss/{name}", meters[5].avg, epoch)
         return iou
 
     def _run_epoch(self, loader, epoch, train):
-        meters = [AverageMeter() for _ in range(5)]
+        lovasz = self.lovasz_ratio != 0
+        meters = [AverageMeter() for _ in range(6 if lovasz else 5)]
         counts = torch.zeros(6, dtype=torch.int64, device=self.device)
-        sums = torch.zeros(5, dtype=torch.float64, device=self.device)  # device-side meters
+        sums = torch.zeros(len(meters), dtype=torch.float64, device=self.device)  # device-side meters
         n_seen = 0
         desc = f"{'Training' if train else 'Validating'} Epoch {epoch + 1}"
         bsamp = getattr(loader, "batch_sampler", None)
         if hasattr(bsamp, "set_epoch"):  # DataParallelShardSampler: same batches on every rank
             bsamp.set_epoch(epoch)
-        nb_extra = 2 if self.config.boundary_ratio != 0 else 0
+        nb_extra = self._extra_reduces()
         for batch in tqdm(loader, desc=desc, leave=True):
             # utils/trainer.py:62-78: the mixup draws (random, numpy beta, then a CPU
             # torch.randperm of the batch size) come first and are consumed alike on every
@@ -272,7 +302,8 @@ class Trainer:
                     logits = self.model(images)
                     loss, l, lb, total = self._losses(logits, masks)
             bs = masks.size(0)
-            sums += torch.stack([l[0], l[1], l[2], lb, total]).detach().double() * bs
+            vals = [l[0], l[1], l[2], lb, total] + ([self._lovasz] if lovasz else [])
+            sums += torch.stack(vals).detach().double() * bs
             n_seen += bs
             self.rt.mask_counts(logits.detach(), masks, counts)
         totals, n_glob = self._reduce_scalars(sums, n_seen)
