@@ -38,6 +38,9 @@
  *                                                           fill holes (scipy's binary_fill_holes)
  *   unet_lesion_stats / _host       (new)                  per-sample component counts of prediction
  *                                                           and target and how many of each are hit
+ *   unet_morphometry / _host        (new)                  per-component size and shape integers of
+ *                                                           a label plane: area, moments, box, bit
+ *                                                           quads, squared maximum Feret diameter
  *   unet_tta_views / _host          (new)                  flip / rotation test-time augmentation:
  *                                                           the dihedral views of a batch, view-major
  *   unet_tta_merge / _host          (new)                  un-warp the per-view logits, average
@@ -395,6 +398,35 @@ int unet_lesion_stats(unet_ctx* ctx, const void* pred, int kind, const float* ta
 int unet_lesion_stats_host(const void* pred, int kind, const float* targets, int N, int C, int H,
                            int W, int connectivity, int64_t* out);
 
+/* Lesion morphometry: the size and shape integers of every connected component (csrc/morph.h;
+ * kernels in csrc/kernels_morph.hip).  labels int32[N, H, W] and count int32[N] as unet_components
+ * writes them (0 background, 1..count[n] the components).  table int64[N, max_rows, 16], the row of
+ * label l at index l - 1, with x the column, y the row and the sums over the component's pixels:
+ *    0      area                          1, 2   sx, sy            3, 4, 5  sxx, sxy, syy
+ *    6..9   x0, y0, x1, y1 (inclusive bounding box)
+ *   10..13  q1, q2, qd, q3: the 2 x 2 windows of the zero-padded plane, (H + 1) (W + 1) of them, in
+ *           which the component's own indicator has one pixel, two edge-adjacent, two diagonal, three
+ *           (perimeter and Euler number follow; four set from q1 + 2 q2 + 2 qd + 3 q3 + 4 q4 = 4 area)
+ *   14      d2max: the largest dx^2 + dy^2 over the component's pixel pairs (squared maximum Feret
+ *           diameter between pixel centres; 0 for one pixel)
+ *   15      first: the component's smallest linear index y W + x
+ * Rows at or beyond count[n] are zero.  A component whose label exceeds max_rows is dropped without a
+ * memory access; count[n] > max_rows tells the caller.  All integer and exact: the device, the host
+ * twin and a NumPy restatement agree bit for bit, whatever the order of the atomics.  Phases: a
+ * reduce pass (64-column tiles, the runs of a tile row from one wave ballot, closed-form run sums,
+ * a label-keyed LDS table per block before the 64-bit global atomics), a row-extent pass behind a
+ * scan of the box heights (at most H ceil(W / 2) (component, row) slots per sample) and one block
+ * per table row over the pairs of its row extremes.  No kernel waits for another block.
+ * A null pointer, N, H, W or max_rows < 1, or H * W >= 2^31 is UNET_ERR_INVALID; H or W above 4096
+ * (which keeps sxx, sxy, syy below 2^48), or N * max_rows >= 2^31, is UNET_ERR_SHAPE.  labels, count
+ * and table are device memory; all work is enqueued on `stream` with no host synchronisation; the
+ * offsets and extents live in a context-owned scratch grown on demand (one stream per context, or
+ * ordered streams).  unet_morphometry_host is the HOST twin (host pointers, the same morph.h rules). */
+int unet_morphometry(unet_ctx* ctx, const int32_t* labels, const int32_t* count, int N, int H, int W,
+                     int64_t max_rows, int64_t* table, unet_stream_t stream);
+int unet_morphometry_host(const int32_t* labels, const int32_t* count, int N, int H, int W,
+                          int64_t max_rows, int64_t* table);
+
 /* Flip / rotation test-time augmentation (csrc/tta.h; kernels in csrc/kernels_tta.hip).  View k in
  * 0..7 has bits h = k & 1, v = (k >> 1) & 1, t = (k >> 2) & 1:
  *   T_k(x): y = x;  if t: y = y.swapaxes(-1, -2);  if v: y = y[..., ::-1, :];  if h: y = y[..., ::-1]
@@ -641,7 +673,7 @@ int unet_overlay_u8_host(const uint8_t* gray, const uint8_t* pred, const uint8_t
  *   tile_n32 tile_convt64 tile_convt tile_convt_dgrad rg16 rg16_tile rg16_bn_k rg16_r3 rg16_n128
  *   rg16_n128_bn wg16 wg16_tile wg16_r3 convt16 wg16t xcd16 xcd_remap dz_in_wgrad x3 x3_tile
  *   x3_wtile x3_wblocks x3_n64 x3_r3 head_fuse pool_fuse x3_wwaves x3_wwaves1 tile_group
- *   cc_tile
+ *   cc_tile morph_lds
  * Set them between steps, not between a forward and its backward: the workspace plan and
  * which saved images exist depend on them (x3, convt16, the bf16 kernel choices, ...), so
  * unet_backward returns UNET_ERR_INVALID when any option differs from those of the training

@@ -205,6 +205,28 @@ void postprocess_host(const void* src, int kind, int N, int C, int H, int W, int
 void lesion_stats_host(const void* pred, int kind, const float* targets, int N, int C, int H, int W,
                        int conn, int64_t* out);
 
+// Lesion morphometry (kernels_morph.hip; fields, rules and the host twin in morph.h): the table
+// int64 [N][max_rows][16] of the label planes unet_components writes.  The phases are separate
+// launchers so that the context can time each one; reduce also initialises the table, extent
+// clears and fills the row extents behind the box heights' offsets, feret finishes every row.
+// scratch holds morph_scratch(...).bytes.  The callers have checked the arguments.
+struct MorphScratch {
+    int64_t* off;      // N max_rows: first extent slot of every table row
+    int* ext;          // N slots (component, row) extents, two ints each
+    int64_t slots;     // ... per sample
+    size_t ext_bytes;  // the part every call zeroes
+    size_t bytes;
+};
+MorphScratch morph_scratch(void* base, int N, int H, int W, int64_t max_rows);
+bool morph_grid_ok(int N, int H, int W, int64_t max_rows);
+// use_lds 0: every contribution straight to global memory (the A/B of tools/morph_time.py)
+int k_morph_reduce(const int* labels, int N, int H, int W, int64_t max_rows, int use_lds, int64_t* table,
+                   hipStream_t s);
+int k_morph_extent(const int* labels, const int* count, int N, int H, int W, int64_t max_rows, const int64_t* table,
+                   const MorphScratch& sc, hipStream_t s);
+int k_morph_feret(const int* count, int N, int H, int W, int64_t max_rows, const MorphScratch& sc, int64_t* table,
+                  hipStream_t s);
+
 // Test-time augmentation (kernels_tta.hip; rules in tta.h): the views of x, view-major, and the
 // merge of the per-view logits.  The callers have checked the arguments (ops_abi.hip).
 int k_tta_views(const float* x, int N, int C, int H, int W, uint32_t views, float* out, hipStream_t s);

@@ -1,5 +1,5 @@
 // The stand-alone entry points of include/unet_hip.h: losses, distance transform, surface and
-// lesion metrics, the Lovasz hinge loss, connected components, test-time augmentation, the threshold sweep, the predict-mode
+// lesion metrics, the Lovasz hinge loss, connected components, lesion morphometry, test-time augmentation, the threshold sweep, the predict-mode
 // export (resize back + overlay), resize and the training augmentations, each with its host twin where
 // it has one.  None of them reads the layer graph
 // or a workspace plan (runtime.hip): they use the context's device, error string, launch timer
@@ -12,6 +12,7 @@
 #include "curve.h"
 #include "edt.h"
 #include "export.h"
+#include "morph.h"
 #include "tta.h"
 #include "x3_split.h"
 
@@ -344,6 +345,36 @@ int unet_lesion_stats_host(const void* pred, int kind, const float* targets, int
                            int connectivity, int64_t* out) {
     if (!pred || !targets || !out || cc_args_error(kind, N, C, H, W, connectivity)) return UNET_ERR_INVALID;
     return catch_to_status([&] { lesion_stats_host(pred, kind, targets, N, C, H, W, connectivity, out); });
+}
+
+// ---- lesion morphometry (kernels_morph.hip, morph.h) ----
+int unet_morphometry(unet_ctx* c, const int32_t* labels, const int32_t* count, int N, int H, int W,
+                     int64_t max_rows, int64_t* table, unet_stream_t stream) {
+    ABI_TRY
+    if (!c) return UNET_ERR_INVALID;
+    if (const char* e = morph_args_invalid(labels, count, table, N, H, W, max_rows))
+        return fail(c, UNET_ERR_INVALID, "morphometry: %s", e);
+    if (!morph_shape_ok(H, W)) return fail(c, UNET_ERR_SHAPE, "morphometry: H, W <= %d", MORPH_MAX_SIDE);
+    if (!morph_grid_ok(N, H, W, max_rows))
+        return fail(c, UNET_ERR_SHAPE, "morphometry: batch too large for one launch");
+    if (int r = grow(c, c->morph, morph_scratch(nullptr, N, H, W, max_rows).bytes, "morphometry")) return r;
+    const MorphScratch sc = morph_scratch(c->morph.p, N, H, W, max_rows);
+    Launcher ln{c, (hipStream_t)stream};
+    const int lds = c->opt.morph_lds;
+    if (int r = ln.run("morph/reduce", 0, [&] { return k_morph_reduce(labels, N, H, W, max_rows, lds, table, ln.s); }))
+        return r;
+    if (int r = ln.run("morph/extent", 0,
+                       [&] { return k_morph_extent(labels, count, N, H, W, max_rows, table, sc, ln.s); }))
+        return r;
+    return ln.run("morph/feret", 0, [&] { return k_morph_feret(count, N, H, W, max_rows, sc, table, ln.s); });
+    ABI_CATCH(c)
+}
+
+int unet_morphometry_host(const int32_t* labels, const int32_t* count, int N, int H, int W, int64_t max_rows,
+                          int64_t* table) {
+    if (morph_args_invalid(labels, count, table, N, H, W, max_rows)) return UNET_ERR_INVALID;
+    if (!morph_shape_ok(H, W)) return UNET_ERR_SHAPE;
+    return catch_to_status([&] { morphometry_host(labels, count, N, H, W, max_rows, table); });
 }
 
 // ---- test-time augmentation (kernels_tta.hip, tta.h) ----

@@ -88,6 +88,7 @@ const OptionDesc OPTION_TABLE[] = {
     {"x3_wwaves1", &Options::x3_wwaves1},
     {"tile_group", &Options::tile_group},
     {"cc_tile", &Options::cc_tile},
+    {"morph_lds", &Options::morph_lds},
 };
 
 // Parameter table in the reference's named_parameters() order, layer tables, packing
@@ -2043,7 +2044,7 @@ int unet_destroy(unet_ctx* c) {
     // (a retired buffer implies a live scratch; nothing allocated: no device call at all)
     void* const own[] = {c->pp,      c->pp3,       c->loss.p,    c->boundary.p, c->clahe.p,
                          c->elastic.p, c->surface.p, c->cc.p,    c->curve.p,   c->exportbuf.p,
-                         c->lovasz.p};
+                         c->lovasz.p,  c->morph.p};
     if (std::any_of(std::begin(own), std::end(own), [](void* p) { return p != nullptr; })) {
         (void)hipSetDevice(c->device);
         for (void* p : own)

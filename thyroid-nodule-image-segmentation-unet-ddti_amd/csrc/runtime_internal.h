@@ -145,6 +145,9 @@ struct Options {
                                // bit-identical
     int cc_tile = 1;           // connected components: tile rows (0 = 16, 1 = 32, 2 = 64; 64 columns);
                                // same labels for every value (profiles/cc_time.txt)
+    int morph_lds = 1;         // lesion morphometry: the reduce pass aggregates per block in an LDS table
+                               // (0 = every run straight to global atomics; same table either way,
+                               // profiles/morph_time.txt)
 };
 
 // A device buffer one feature's entry points own through the context, grown on demand (grow):
@@ -245,6 +248,7 @@ struct unet_ctx {
     Scratch curve;     // unet_curve_stats: the planes' dice_k before their ordered sum
     Scratch exportbuf; // unet_resize_f32_mask: the float32 intermediate of the horizontal pass
     Scratch lovasz;    // unet_lovasz_fwd: the sort's key / word buffers, histograms, tile sums
+    Scratch morph;     // unet_morphometry: row offsets and row extents of the components
     std::vector<void*> retired;
 
     int nconv() const { return (int)conv.size(); }

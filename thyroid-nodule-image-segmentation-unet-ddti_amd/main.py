@@ -138,6 +138,15 @@ def get_parser(argv=None):
     p.add_argument("--lesion_metrics", action="store_true",
                    help="test: also report lesion-level recall, precision and false-positive "
                         "components per image (of the cleaned masks when a --pp_* option is set)")
+    p.add_argument("--lesion_table", action="store_true",
+                   help="predict: also write lesions.csv, one line per connected component of every frame's "
+                        "final mask (size, position, Feret diameter, axes, perimeter, holes, taller-than-wide), "
+                        "measured on the GPU at --pp_connectivity")
+    p.add_argument("--pixel_spacing", type=float, default=None, metavar="MM",
+                   help="--lesion_table: millimetres per pixel; adds feret_max_mm and area_mm2")
+    p.add_argument("--lesion_shape", action="store_true",
+                   help="test: also report how the largest predicted lesion's size and shape agree with the "
+                        "annotated one's (Feret diameter, area, centroid, taller-than-wide), measured on the GPU")
     p.add_argument("--tta", default="none", choices=("none", "hflip", "flips", "d4"),
                    help="test: also predict the flipped (hflip: 2 views, flips: 4) or flipped and "
                         "rotated (d4: 8) images, un-warp and merge on the GPU; a second block reports "
@@ -156,11 +165,25 @@ def get_parser(argv=None):
     args = p.parse_args(argv)
     if not 0 <= args.overlay_alpha <= 256:
         p.error(f"--overlay_alpha must be in 0..256, got {args.overlay_alpha}")
+    e = lesion_args_error(args)
+    if e:
+        p.error(e)
     if args.mode == "predict":
         e = predict_args_error(args, int(os.environ.get("WORLD_SIZE", "1")))
         if e:
             p.error(e)
     return args
+
+
+def lesion_args_error(args):
+    """What the lesion-table flags refuse, as a message (None: nothing)."""
+    if args.lesion_table and args.mode != "predict":
+        return f"--lesion_table writes lesions.csv in --mode predict only (got --mode {args.mode})"
+    if args.pixel_spacing is not None and not args.pixel_spacing > 0:
+        return f"--pixel_spacing must be positive millimetres per pixel, got {args.pixel_spacing}"
+    if args.pixel_spacing is not None and not args.lesion_table:
+        return "--pixel_spacing scales the columns of --lesion_table; pass that too"
+    return None
 
 
 def predict_args_error(args, world=1):
@@ -204,7 +227,7 @@ def predict(args):
     --batch_size; masks, overlays and predictions.csv into --output_dir."""
     from PIL import Image
 
-    from unet_hip.predict import CSV_HEADER, Predictor, save_predictions
+    from unet_hip.predict import CSV_HEADER, Predictor, lesion_csv_header, lesion_lines, save_predictions
     if args.model_type not in ("UNet", "ModUNet", "ResUNet"):
         raise SystemExit(f"model_type {args.model_type!r}: the HIP path has UNet, ModUNet and ResUNet")
     set_seed(seed=42)
@@ -225,15 +248,22 @@ def predict(args):
                      threshold=args.threshold,
                      pp=dict(keep_largest=args.pp_largest, min_area=args.pp_min_area, fill_holes=args.pp_fill_holes,
                              connectivity=args.pp_connectivity),
-                     width=args.contour_width, alpha=args.overlay_alpha, bins=args.curve_bins)
+                     width=args.contour_width, alpha=args.overlay_alpha, bins=args.curve_bins,
+                     lesion_table=args.lesion_table)
     lines = [",".join(CSV_HEADER)]
+    lesions = [",".join(lesion_csv_header(args.pixel_spacing))]
     for start in range(0, len(names), args.batch_size):
         chunk = names[start:start + args.batch_size]
         planes = [decode_u8(Image.open(os.path.join(args.input_dir, n))) for n in chunk]
         out = pred(planes, return_scores=args.save_prob)
         lines += save_predictions(out, chunk, args.output_dir, save_scores=args.save_prob)
+        if args.lesion_table:
+            lesions += lesion_lines(out, chunk, args.pixel_spacing, args.pp_connectivity)
     with open(os.path.join(args.output_dir, "predictions.csv"), "w") as f:
         f.write("\n".join(lines) + "\n")
+    if args.lesion_table:
+        with open(os.path.join(args.output_dir, "lesions.csv"), "w") as f:
+            f.write("\n".join(lesions) + "\n")
     print(f"[PREDICT] {len(names)} images -> {args.output_dir}")
 
 

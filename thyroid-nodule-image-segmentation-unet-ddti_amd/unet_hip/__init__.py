@@ -12,10 +12,11 @@ from ._lib import HipError, HipUnavailable, LIB_PATH, load  # noqa: F401
 from .data import GpuResizeToTensor  # noqa: F401
 from .functional import (LovaszHingeFunction, boundary_loss, connected_components, connected_components_host,  # noqa: F401
                          curve_edges, curve_hist, curve_hist_host, curve_stats, curve_stats_host,
-                         curve_summary, distance_maps, lesion_metrics, lesion_metrics_host, lovasz_hinge,
+                         curve_summary, distance_maps, lesion_metrics, lesion_metrics_host,
+                         lesion_morphometry, lesion_morphometry_host, lovasz_hinge,
                          lovasz_hinge_host, lovasz_hinge_parts, overlay,
-                         overlay_host, postprocess_mask, postprocess_mask_host, resize_back, resize_back_host,
-                         seg_losses, surface_metrics, surface_metrics_host,
+                         morphometry_table, morphometry_table_host, overlay_host, postprocess_mask, postprocess_mask_host, resize_back, resize_back_host,
+                         seg_losses, shape_descriptors, surface_metrics, surface_metrics_host,
                          tta_merge, tta_merge_host, tta_predict, tta_views, tta_views_host)
 from .module import ModUNet, ResUNet, UNet  # noqa: F401
 from .optim import HipAdamW  # noqa: F401

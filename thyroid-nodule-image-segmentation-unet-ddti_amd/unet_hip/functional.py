@@ -401,6 +401,193 @@ def lesion_metrics_host(pred, targets, connectivity=1, kind=None):
     return {f: out[:, i] for i, f in enumerate(LESION_FIELDS)}
 
 
+# ---------------------------------------------------------------- lesion morphometry
+MORPH_FIELDS = ("area", "sx", "sy", "sxx", "sxy", "syy", "x0", "y0", "x1", "y1", "q1", "q2", "qd", "q3", "d2max",
+                "first")
+LESION_COLUMNS = ("name", "label", "area", "centroid_x", "centroid_y", "x0", "y0", "x1", "y1", "feret_max",
+                  "major_axis", "minor_axis", "orientation", "eccentricity", "perimeter", "circularity", "holes",
+                  "taller_than_wide")
+LESION_COLUMNS_MM = ("feret_max_mm", "area_mm2")
+
+
+def _morph_args(labels, count, max_rows):
+    """labels as contiguous int32 (N, H, W), count as int32 (N,), max_rows as an int (None: the
+    largest count, at least 1; reading it is the caller's one synchronisation)."""
+    labels, count = labels.detach(), count.detach()
+    if labels.dim() == 2:
+        labels = labels[None]
+    if labels.dim() != 3 or labels.dtype != torch.int32:
+        raise ValueError(f"labels must be int32 (H, W) or (N, H, W), got {labels.dtype} {tuple(labels.shape)}")
+    count = count.reshape(-1)
+    if count.dtype != torch.int32 or count.numel() != labels.shape[0] or count.device != labels.device:
+        raise ValueError(f"count must be int32 ({labels.shape[0]},) on the labels' device, got {count.dtype} "
+                         f"{tuple(count.shape)} on {count.device}")
+    if max_rows is None:
+        max_rows = max(int(count.max()), 1)
+    return labels.contiguous(), count.contiguous(), int(max_rows)
+
+
+def morphometry_table(labels, count, max_rows=None):
+    """The size and shape integers of every component of the label planes ``connected_components``
+    returned, on the device and the current stream: int64 (N, max_rows, 16), row l - 1 for label l,
+    the columns in ``MORPH_FIELDS`` order (area; sx, sy, sxx, sxy, syy over the pixels' column x and
+    row y; the inclusive box x0, y0, x1, y1; the bit-quad counts q1, q2, qd, q3; d2max, the squared
+    maximum Feret diameter between pixel centres; first, the smallest linear index).  Rows beyond
+    count[n] are zero and components beyond max_rows are dropped (count says so).  All integer and
+    exact.  max_rows=None reads ``count.max()`` (the only host synchronisation)."""
+    rt = _boundary_runtime(labels, "morphometry_table")
+    labels, count, max_rows = _morph_args(labels, count, max_rows)
+    return rt.morphometry(labels, count, max_rows)
+
+
+def morphometry_table_host(labels, count, max_rows=None):
+    """``morphometry_table`` of CPU tensors through the library's host twin."""
+    _cc_cpu(labels, "morphometry_table_host")
+    labels, count, max_rows = _morph_args(labels, count, max_rows)
+    N, H, W = labels.shape
+    table = torch.empty((N, max(max_rows, 0), 16), dtype=torch.int64)
+    _cc_host_call("unet_morphometry_host", labels, count, N, H, W, max_rows, table)
+    return table
+
+
+def lesion_morphometry(x, connectivity=1, kind=None, max_rows=None):
+    """``connected_components`` of x, then ``morphometry_table`` of its labels, on the device: a dict
+    of ``table`` int64 (N, max_rows, 16), ``count`` int32 (N,) and ``labels`` int32 (N, H, W)."""
+    labels, count = connected_components(x, connectivity, kind)
+    return {"table": morphometry_table(labels, count, max_rows), "count": count, "labels": labels}
+
+
+def lesion_morphometry_host(x, connectivity=1, kind=None, max_rows=None):
+    """``lesion_morphometry`` of a CPU tensor through the library's host twins."""
+    labels, count = connected_components_host(x, connectivity, kind)
+    return {"table": morphometry_table_host(labels, count, max_rows), "count": count, "labels": labels}
+
+
+def shape_descriptors(table, spacing=1.0, connectivity=1):
+    """Shape descriptors of the rows of a morphometry table, in NumPy float64 on the host from the
+    integer rows alone.  table: int64 (..., 16) (a tensor or an array); every returned array has the
+    shape ``table.shape[:-1]``, and a row without pixels gives zeros.  x is the column, y the row
+    (y grows downwards); lengths are multiplied by ``spacing``, areas by ``spacing ** 2``.
+
+    ``area``; ``centroid_x``, ``centroid_y`` = sx / area, sy / area; ``mu20``, ``mu11``, ``mu02`` the
+    normalised second central moments, e.g. (area sxx - sx^2) / area^2 with the numerator formed in
+    Python integers before the one division; ``major_axis``, ``minor_axis`` = 4 sqrt(lambda) of the
+    eigenvalues of [[mu20, mu11], [mu11, mu02]] (the axes of the ellipse with the same moments);
+    ``orientation`` the angle of the major axis from the x axis towards the y axis, radians in
+    (-pi/2, pi/2]; ``eccentricity`` = sqrt(1 - lambda_min / lambda_max); ``feret_max`` = sqrt(d2max);
+    ``box_w``, ``box_h``; ``taller_than_wide`` = box_h > box_w (image rows run along the beam, so on
+    a transverse frame this is the TI-RADS taller-than-wide sign: the antero-posterior extent exceeds
+    the transverse one); ``extent`` = area / box area; ``perimeter_crack`` = q1 + q2 + q3 + 2 qd
+    (the pixel-edge length of the outline, holes included); ``perimeter`` = q2 + (q1 + q3 + 2 qd) /
+    sqrt(2) (the bit-quad estimate); ``circularity`` = 4 pi area / perimeter^2; ``euler`` = (q1 - q3
+    + 2 qd) / 4 at connectivity 1, (q1 - q3 - 2 qd) / 4 at 2; ``holes`` = 1 - euler."""
+    import math
+
+    import numpy as np
+    if connectivity not in (1, 2):
+        raise ValueError(f"connectivity must be 1 or 2, got {connectivity!r}")
+    spacing = float(spacing)
+    if not spacing > 0:
+        raise ValueError(f"spacing must be positive, got {spacing!r}")
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    if t.shape[-1:] != (16,) or t.dtype != np.int64:
+        raise ValueError(f"table must be int64 (..., 16), got {t.dtype} {t.shape}")
+    shape = t.shape[:-1]
+    rows = t.reshape(-1, 16)
+    names = ("area", "centroid_x", "centroid_y", "mu20", "mu11", "mu02", "major_axis", "minor_axis", "orientation",
+             "eccentricity", "feret_max", "box_w", "box_h", "extent", "perimeter_crack", "perimeter", "circularity",
+             "euler", "holes")
+    out = {k: np.zeros(len(rows), np.float64) for k in names}
+    out["taller_than_wide"] = np.zeros(len(rows), bool)
+    out["euler"] = np.zeros(len(rows), np.int64)
+    out["holes"] = np.zeros(len(rows), np.int64)
+    s2 = spacing * spacing
+    for i, r in enumerate(rows.tolist()):  # Python ints: the central moments pass 2^64
+        a, sx, sy, sxx, sxy, syy, x0, y0, x1, y1, q1, q2, qd, q3, d2, _ = r
+        if a <= 0:
+            continue
+        a2 = a * a
+        m20, m11, m02 = (a * sxx - sx * sx) / a2, (a * sxy - sx * sy) / a2, (a * syy - sy * sy) / a2
+        mid, dev = (m20 + m02) / 2, math.hypot((m20 - m02) / 2, m11)
+        l1, l2 = mid + dev, max(mid - dev, 0.0)
+        bw, bh = x1 - x0 + 1, y1 - y0 + 1
+        per = q2 + (q1 + q3 + 2 * qd) / math.sqrt(2.0)
+        e4 = q1 - q3 + 2 * qd if connectivity == 1 else q1 - q3 - 2 * qd
+        out["area"][i] = a * s2
+        out["centroid_x"][i] = sx / a * spacing
+        out["centroid_y"][i] = sy / a * spacing
+        out["mu20"][i], out["mu11"][i], out["mu02"][i] = m20 * s2, m11 * s2, m02 * s2
+        out["major_axis"][i] = 4 * math.sqrt(l1) * spacing
+        out["minor_axis"][i] = 4 * math.sqrt(l2) * spacing
+        out["orientation"][i] = 0.5 * math.atan2(2 * m11, m20 - m02) if dev > 0 else 0.0
+        out["eccentricity"][i] = math.sqrt(max(1 - l2 / l1, 0.0)) if l1 > 0 else 0.0
+        out["feret_max"][i] = math.sqrt(d2) * spacing
+        out["box_w"][i], out["box_h"][i] = bw * spacing, bh * spacing
+        out["taller_than_wide"][i] = bh > bw
+        out["extent"][i] = a / (bw * bh)
+        out["perimeter_crack"][i] = (q1 + q2 + q3 + 2 * qd) * spacing
+        out["perimeter"][i] = per * spacing
+        out["circularity"][i] = 4 * math.pi * a / (per * per)
+        out["euler"][i] = e4 // 4
+        out["holes"][i] = 1 - e4 // 4
+    return {k: v.reshape(shape) for k, v in out.items()}
+
+
+SHAPE_SUMS = ("n_pairs", "feret_abs", "area_rel", "centroid_dist", "ttw_both", "ttw_pred_only", "ttw_gt_only",
+              "ttw_neither")
+
+
+def shape_agreement(pred_rows, gt_rows):
+    """How the size and shape of predicted lesions agree with the annotated ones: pred_rows, gt_rows
+    int64 (n, 16), one table row per sample (its largest component; area 0 = none).  Over the pairs
+    with both present, a float64 (8,) array in ``SHAPE_SUMS`` order: the pairs, the sums of
+    |feret_max difference| (pixels), of |area_pred - area_gt| / area_gt and of the centroid distance,
+    and the 2 x 2 counts of ``taller_than_wide`` (both, prediction only, annotation only, neither)."""
+    import numpy as np
+    dp, dg = shape_descriptors(pred_rows), shape_descriptors(gt_rows)
+    both = (dp["area"] > 0) & (dg["area"] > 0)
+    tp, tg = dp["taller_than_wide"][both], dg["taller_than_wide"][both]
+    return np.array([both.sum(), np.abs(dp["feret_max"] - dg["feret_max"])[both].sum(),
+                     (np.abs(dp["area"] - dg["area"])[both] / dg["area"][both]).sum(),
+                     np.hypot(dp["centroid_x"] - dg["centroid_x"], dp["centroid_y"] - dg["centroid_y"])[both].sum(),
+                     (tp & tg).sum(), (tp & ~tg).sum(), (~tp & tg).sum(), (~tp & ~tg).sum()], np.float64)
+
+
+def shape_summary(sums):
+    """The SHAPE block's numbers from the ``SHAPE_SUMS`` (summed over the test set): ``n_pairs``, the
+    means ``feret_mae``, ``area_rel_err`` and ``centroid_dist`` (nan without a pair), the agreement
+    counts ``ttw`` and Cohen's ``kappa`` of them (nan when chance agreement is 1)."""
+    n, fe, ar, ce, a, b, c, d = (float(v) for v in sums)
+    nan = float("nan")
+    out = dict(n_pairs=int(n), feret_mae=fe / n if n else nan, area_rel_err=ar / n if n else nan,
+               centroid_dist=ce / n if n else nan, ttw=[int(a), int(b), int(c), int(d)])
+    pe = ((a + b) * (a + c) + (c + d) * (b + d)) / (n * n) if n else 1.0
+    out["kappa"] = ((a + d) / n - pe) / (1 - pe) if pe != 1.0 else nan
+    return out
+
+
+def lesion_csv_lines(name, table, count, pixel_spacing=None, connectivity=1):
+    """The lines of lesions.csv (no newline) for one frame: one per component, the ``LESION_COLUMNS``
+    in pixels (integers as such, real numbers with four decimals, the orientation in radians), then
+    with a spacing in millimetres per pixel the ``LESION_COLUMNS_MM``.  table: int64 (rows, 16), count:
+    the frame's component count (rows beyond the table were dropped and write no line)."""
+    k = min(int(count), int(table.shape[0]))
+    d = shape_descriptors(table[:k], 1.0, connectivity)
+    rows = (table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table)[:k]
+    lines = []
+    for i in range(k):
+        f = [str(name), str(i + 1), str(int(rows[i][0])), f"{d['centroid_x'][i]:.4f}", f"{d['centroid_y'][i]:.4f}"]
+        f += [str(int(rows[i][c])) for c in (6, 7, 8, 9)]
+        f += [f"{d[c][i]:.4f}" for c in ("feret_max", "major_axis", "minor_axis", "orientation", "eccentricity",
+                                         "perimeter", "circularity")]
+        f += [str(int(d["holes"][i])), str(int(d["taller_than_wide"][i]))]
+        if pixel_spacing is not None:
+            sp = float(pixel_spacing)
+            f += [f"{d['feret_max'][i] * sp:.4f}", f"{int(rows[i][0]) * sp * sp:.4f}"]
+        lines.append(",".join(f))
+    return lines
+
+
 # ---------------------------------------------------------------- test-time augmentation
 TTA_SETS = {"hflip": 0x03, "flips": 0x0F, "d4": 0xFF}
 TTA_MODES = {"logit": 0, "prob": 1}

@@ -10,6 +10,9 @@ Per batch: ``GpuResizeToTensor`` to the network resolution, the forward (or ``tt
 per frame ``resize_back`` of its score plane to the frame's own (h, w) with the threshold fused in,
 the optional ``postprocess_mask`` there, ``overlay`` on the frame itself and a connected-component
 count.  Nothing comes back to the host but one row of seven integers per frame, in one transfer.
+With ``lesion_table=True`` the labels of that count are kept, the frames of one size share one
+``morphometry_table`` call, and the sixteen integers of every component come back in a second transfer
+(``out["lesions"]``, the rows of lesions.csv).
 """
 import numpy as np
 import torch
@@ -51,7 +54,7 @@ def check_predict_options(tta, threshold):
 
 class Predictor:
     def __init__(self, model, image_size, device, tta="none", tta_merge="prob", threshold=0.5, pp=None, width=1,
-                 alpha=0, bins=256):
+                 alpha=0, bins=256, lesion_table=False):
         self.device = torch.device(device)
         self.model = model.to(self.device).eval()
         self.pipe = GpuResizeToTensor(image_size, self.device)
@@ -75,6 +78,7 @@ class Predictor:
                        fill_holes=bool(pp.get("fill_holes", False)), connectivity=int(pp.get("connectivity", 1) or 1))
         self.post = self.pp["keep_largest"] or self.pp["min_area"] > 0 or self.pp["fill_holes"]
         self.width, self.alpha = int(width), int(alpha)
+        self.lesion_table = bool(lesion_table)
 
     def _forward(self, gray, planes):
         """(N, S, S) float32: the score planes at the network resolution of the uploaded frames
@@ -86,6 +90,25 @@ class Predictor:
             return F.tta_predict(self.model, x, self.tta, self.tta_merge)["score"][:, 0].contiguous()
         return self.model(x).detach().float()[:, 0].contiguous()
 
+    def _lesions(self, labels, counts):
+        """Per frame the int64 (count, 16) table rows on the host: the frames of one size are one
+        ``morphometry_table`` call (max_rows their largest count), all tables one transfer."""
+        groups = {}
+        for i, (lab, _) in enumerate(labels):
+            if counts[i] > 0:
+                groups.setdefault(tuple(lab.shape[1:]), []).append(i)
+        flat, where = [], {}
+        for idx in groups.values():
+            rows = max(counts[i] for i in idx)
+            tab = F.morphometry_table(torch.cat([labels[i][0] for i in idx]), torch.cat([labels[i][1] for i in idx]),
+                                      rows)
+            for j, i in enumerate(idx):
+                where[i] = (sum(t.shape[0] for t in flat), counts[i])
+                flat.append(tab[j, :counts[i]])
+        back = torch.cat(flat).cpu() if flat else torch.zeros((0, 16), dtype=torch.int64)  # the one transfer
+        empty = torch.zeros((0, 16), dtype=torch.int64)
+        return [back[where[i][0]:where[i][0] + where[i][1]] if i in where else empty for i in range(len(labels))]
+
     @torch.no_grad()
     def scores(self, planes):
         """(N, S, S) float32: the score planes of the frames at the network resolution."""
@@ -96,10 +119,12 @@ class Predictor:
         """planes: a list of (h, w) uint8 frames (arrays or tensors, any sizes).  Returns a dict of
         lists, one entry per frame: ``masks`` (uint8 (h, w) in {0, 1}), ``overlays`` (uint8 (h, w, 3)),
         ``scores`` (float32 (h, w), when asked), all on the device, and ``rows`` (dicts of Python ints:
-        h, w, area, contour, x0, y0, x1, y1, components).  Every frame is uploaded once."""
+        h, w, area, contour, x0, y0, x1, y1, components).  Every frame is uploaded once.  With
+        ``lesion_table``, ``lesions`` too: per frame the int64 (components, 16) rows of
+        ``morphometry_table`` on the host."""
         grays = [self.pipe.upload(im) for im in planes]
         score = self._forward(grays, planes)
-        masks, overlays, planes_out, stats = [], [], [], []
+        masks, overlays, planes_out, stats, labels = [], [], [], [], []
         for i, gray in enumerate(grays):
             h, w = gray.shape
             out = F.resize_back(score[i], (h, w), self.kind, self.thr, return_plane=return_scores)
@@ -107,7 +132,9 @@ class Predictor:
             if self.post:
                 mask = F.postprocess_mask(mask, **self.pp)[0][0]
             rgb, st = F.overlay(gray, mask, None, self.width, self.alpha)
-            _, count = F.connected_components(mask, self.pp["connectivity"])
+            lab, count = F.connected_components(mask, self.pp["connectivity"])
+            if self.lesion_table:
+                labels.append((lab, count))
             masks.append(mask)
             overlays.append(rgb)
             planes_out.append(sc)
@@ -119,9 +146,25 @@ class Predictor:
             row.update(zip(ROW_FIELDS, (int(v) for v in r)))
             rows.append(row)
         out = dict(masks=masks, overlays=overlays, rows=rows)
+        if self.lesion_table:
+            out["lesions"] = self._lesions(labels, [r["components"] for r in rows])
         if return_scores:
             out["scores"] = planes_out
         return out
+
+
+def lesion_lines(out, names, pixel_spacing=None, connectivity=1):
+    """The lines of lesions.csv (no header) for what a ``Predictor`` with ``lesion_table`` returned for
+    the frames ``names``: one per component, none for an empty mask (``F.lesion_csv_lines``)."""
+    import os
+    lines = []
+    for name, tab in zip(names, out["lesions"]):
+        lines += F.lesion_csv_lines(os.path.basename(name), tab, tab.shape[0], pixel_spacing, connectivity)
+    return lines
+
+
+def lesion_csv_header(pixel_spacing=None):
+    return F.LESION_COLUMNS + (F.LESION_COLUMNS_MM if pixel_spacing is not None else ())
 
 
 def save_predictions(out, names, output_dir, save_scores=False):

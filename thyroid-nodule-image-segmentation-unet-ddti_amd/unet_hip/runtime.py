@@ -277,6 +277,16 @@ class UNetRuntime:
         _lib.check(rc, self.ctx, "unet_lesion_stats")
         return out
 
+    def morphometry(self, labels, count, max_rows):
+        """table int64 (N, max_rows, 16) of labels int32 (N, H, W) and count int32 (N,)
+        (unet_morphometry; the fields in csrc/morph.h)."""
+        N, H, W = labels.shape
+        table = torch.empty((N, max_rows, 16), dtype=torch.int64, device=labels.device)
+        rc = self.lib.unet_morphometry(self.ctx, _lib.ptr(labels), _lib.ptr(count), N, H, W, max_rows,
+                                       _lib.ptr(table), _lib.stream_ptr(labels.device))
+        _lib.check(rc, self.ctx, "unet_morphometry")
+        return table
+
     def tta_views(self, x, views):
         """(K N, C, H, W): the views of x (N, C, H, W) in ascending k, view-major (unet_tta_views;
         views is the bit mask)."""

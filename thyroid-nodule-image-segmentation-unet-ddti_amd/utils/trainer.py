@@ -375,6 +375,8 @@ class Trainer:
                   connectivity=int(getattr(cfg, "pp_connectivity", 1) or 1))
         post = pp["keep_largest"] or pp["min_area"] > 0 or pp["fill_holes"]
         lesion = bool(getattr(cfg, "lesion_metrics", False))
+        shape = bool(getattr(cfg, "lesion_shape", False))
+        shape_rows = []  # per batch: the table rows of the largest predicted and annotated component
         if post:  # the same sums for the post-processed masks
             pcounts = torch.zeros(6, dtype=torch.int64, device=self.device)
             psums = torch.zeros(5, dtype=torch.float64, device=self.device)
@@ -444,6 +446,9 @@ class Trainer:
             if lesion:
                 les = unet_hip.lesion_metrics(clean if post else mask, masks, pp["connectivity"])
                 lsums += torch.stack([les[k].sum() for k in unet_hip.functional.LESION_FIELDS])
+            if shape:
+                shape_rows.append(torch.cat([self._largest_row(clean if post else mask, pp["connectivity"], None),
+                                             self._largest_row(masks, pp["connectivity"], "targets")], 1))
             total += images.size(0)
             keep.append((images.cpu(), masks.cpu(), mask.cpu()))
         if _distributed():
@@ -552,6 +557,24 @@ class Trainer:
             self.logger.info(omsg)
             m.update({"OPT_" + k: v for k, v in om.items()})
             m["OPT_Threshold"] = opt_k / bins
+        if shape:
+            rows = (torch.cat(shape_rows) if shape_rows else torch.zeros((0, 32), dtype=torch.int64)).cpu()  # the one transfer
+            sums = torch.from_numpy(unet_hip.functional.shape_agreement(rows[:, :16], rows[:, 16:]))
+            if _distributed():
+                sums = sums.to(self.device)
+                dist.all_reduce(sums)
+            sh = unet_hip.functional.shape_summary(sums.tolist())
+            shmsg = (f"SHAPE (largest component, {('post-processed' if post else 'raw') + (' TTA' if tta_on else '')} "
+                     f"masks, connectivity {pp['connectivity']}) — pairs={sh['n_pairs']} of {total} images\n"
+                     f"  Feret MAE={sh['feret_mae']:.4f} px, area rel. error={sh['area_rel_err']:.4f}, "
+                     f"centroid distance={sh['centroid_dist']:.4f} px\n"
+                     f"  taller-than-wide (pred/gt): both={sh['ttw'][0]}, pred only={sh['ttw'][1]}, "
+                     f"gt only={sh['ttw'][2]}, neither={sh['ttw'][3]}, kappa={sh['kappa']:.4f}")
+            if self.rank0:
+                print(shmsg)
+            self.logger.info(shmsg)
+            m.update(Shape_Pairs=sh["n_pairs"], Shape_FeretMAE=sh["feret_mae"], Shape_AreaRelErr=sh["area_rel_err"],
+                     Shape_CentroidDist=sh["centroid_dist"], Shape_TTW=sh["ttw"], Shape_TTWKappa=sh["kappa"])
         if _distributed() and (self._can_plot() or save_overlays):
             # one set of PNGs over the whole test set, in the reference's sample order: batch
             # by batch, each batch's shards in rank order (DataParallel's gather order)
@@ -566,6 +589,15 @@ class Trainer:
         if save_overlays and self.rank0:
             self._save_overlays(keep)
         return m
+
+    @staticmethod
+    def _largest_row(x, connectivity, kind):
+        """int64 (N, 16): the morphometry row of every sample's largest component (the cc_key rule of
+        ``postprocess_mask``: largest area, then first in raster order; zeros for an empty mask), on the
+        device with no synchronisation -- the mask of that component alone has one label, so one table
+        row holds it."""
+        one, _ = unet_hip.postprocess_mask(x, keep_largest=True, connectivity=connectivity, kind=kind)
+        return unet_hip.lesion_morphometry(one, connectivity, max_rows=1)["table"][:, 0]
 
     def _save_overlays(self, keep):
         """One PNG per kept sample (images, targets, predicted mask as CPU batches), rendered on the
