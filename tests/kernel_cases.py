@@ -2,9 +2,9 @@
 residual network main.py trains), and the small fp64-checked cases that stand for them
 (tests/test_gpu_kernel_coverage.py; helper of the tests, not a test; importable without a GPU).
 
-runtime.hip chooses the kernel and tile of every conv / ConvT / skip GEMM from the shape and
-the CU count (x3_tile, x3_wgrad_cfg, rg16_tile, wgrad_cfg, pick_tile, wg16_tile,
-convt_wg16_on), by block-count thresholds the suite's 64^2 / 128^2 inputs never reach.  The
+runtime.hip chooses the kernel and tile of every conv / ConvT / skip GEMM in the plan, from the shape
+and the CU count (plan_tiles: x3_pick, x3_wgrad_cfg, rg16_pick, wgrad_cfg, pick_tile, wg16_pick;
+the tiles are the rows of csrc/tiles.h), by block-count thresholds the suite's 64^2 / 128^2 inputs never reach.  The
 library reports every launch as ``family/kernel_tile|layer`` (rt.timing_records()).  `key`
 reduces such a label to what a small case has to reproduce to stand for it:
 
@@ -217,7 +217,7 @@ def by_id(cases):
 
 def _eval(id, note, **kw):
     """The SMALL case `id` run in eval mode (forward only): same network, shape and options,
-    which reproduce its forward keys -- the tile rules (x3_tile, rg16_tile, pick_tile) read the
+    which reproduce its forward keys -- the tile rules (x3_pick, rg16_pick, pick_tile) read the
     shape and the options, not the mode.  pseed / xseed: parameter and input seeds (7 / 33, the
     coverage test's, unless the meaningful-input condition of tests/test_eval_ref_cpu.py asks
     for others)."""

@@ -170,45 +170,25 @@ struct WgradArgs {
         if (e_ != hipSuccess) return (int)e_;       \
     } while (0)
 
-// host launchers (kernels_gemm.hip)
-// row-GEMM tile ids: register-staged 0 = 128x128 (two LDS images), 1 = 128x64, 4 = 128x128,
-// 6 = 128x128 64-K chunks (bf16), 13 = 128x32, 14 = 256x32; software-pipelined (kernels_gemm_pipe.hip)
-// 18 = 128x128, 19 = 128x64 (loading two chunks ahead), 25 / 26 = 128x64 at three blocks per CU
-// (one / two chunks ahead)
-int launch_rowgemm(const RowGemmArgs& a, int tile, hipStream_t s);
-int rowgemm_tile_dims(int tile, int* bm, int* bn, int* bk);
-int rowgemm_tile_dbuf(int tile);
-// software-pipelined f32 row GEMM (kernels_gemm_pipe.hip); tile 2 = 128x128, 3 = 128x64 (two
-// chunks ahead), 4 / 5 = 128x64 at three blocks per CU
+#include "tiles.h"
+
+// host launchers; `tile` is an id of the family's table in tiles.h
+int launch_rowgemm(const RowGemmArgs& a, int tile, hipStream_t s);          // kernels_gemm.hip
+// software-pipelined f32 row GEMM (kernels_gemm_pipe.hip): the K_PIPE tiles of ROW_TILES
 int rowgemm_pipe_ok(const RowGemmArgs& a);
 int launch_rowgemm_pipe(const RowGemmArgs& a, int tile, hipStream_t s);
-// wgrad tile ids (kernels_gemm.hip WGRAD_TILES): 0 = 128x128, 3 = 64x128 two waves,
-// 5 = 128x64 four waves, 7 = 64x64 three waves / SIMD, 8 = 64x32, 9 = 32x32;
-// 20.. = one row of 3x3 taps per block (3 accumulator sets; BM = channels of ONE tap):
-// 20 = 64x64, 21 = 128x64, 22 = 64x128, 23 = 128x128
-int launch_rowgemm16(const RowGemmArgs& a, int tile, hipStream_t s);
-int rowgemm16_tile_dims(int tile, int* bm, int* bn, int* stages = nullptr);
-int wgrad16g_tile_dims(int tile, int* bm, int* bn, int* stages = nullptr);
-int launch_wgrad(const WgradArgs& a, int tile, hipStream_t s);
+int launch_rowgemm16(const RowGemmArgs& a, int tile, hipStream_t s);        // kernels_gemm16.hip
+int launch_wgrad(const WgradArgs& a, int tile, hipStream_t s);              // a.bf16: WGB_TILES
 int launch_wgrad16(const WgradArgs& a, int tile, hipStream_t s);
-int wgrad_tile_dims(int tile, int* bm, int* bn, int* bkp);
-int wgrad_tile_taps(int tile);  // taps of the M dimension one block covers (3 for 20..)
 // f32 GEMMs on bf16 MFMAs through exact three-way operand splits (kernels_gemm_x3.hip):
 // x3 images bf16 [rows][C / 32][3][32] (hi, mid, lo planes per 32-channel group).  Row GEMM:
-// a16 / bt16 are x3 images (lda channels per A row, aoff a channel offset); tiles 0 =
-// 256x128, 1 = 128x128, 2 = 128x64, 3 = 256x64; tap-row halo tiles 4 = 256x128, 6 = 128x64.
-// Weight gradient: a / b are x3 images; tiles 0 = 128x128, 1 = 64x64; tap-row tiles 2 = 64x128,
-// 4 = 64x64.
+// a16 / bt16 are x3 images (lda channels per A row, aoff a channel offset).  Weight gradient:
+// a / b are x3 images.
 int launch_rowgemm_x3(const RowGemmArgs& a, int tile, hipStream_t s);
-int rowgemm_x3_tile_dims(int tile, int* bm, int* bn);
 int launch_wgrad_x3(const WgradArgs& a, int tile, hipStream_t s);
-int wgrad_x3_tile_dims(int tile, int* bm, int* bn);
 // x3 image of op(src) (BN affine if scale, ReLU on channels < relu) into dst [P][dld] at
 // channel offset doff
 int k_to_x3(const float* src, int ld, int off, int C, const float* scale, const float* shift,
             int relu, int64_t P, uint16_t* dst, int dld, int doff, hipStream_t s);
 // row blocks of the dz pass's x3 output (dz_pass.h): the rows of its bias column partials
 int x3_dz_blocks(int64_t P);
-// register-staged bf16 wgrad tile ids (a.bf16): 0 = 128x128/32 px, 2 = 64x64/64,
-// 3 = 128x64/64, 4 = 64x128/64
-int wgrad16_tile_dims(int tile, int* bm, int* bn, int* bkp);

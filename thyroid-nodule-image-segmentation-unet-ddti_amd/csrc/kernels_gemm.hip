@@ -248,8 +248,8 @@ __global__ __launch_bounds__(T::THREADS, T::OCC) void rowgemm_kernel(RowGemmArgs
 }
 
 // ------------------------------------------------------------------------------------
-// Skinny row GEMM (N = 32 outputs: the narrow networks' level 0; tile 15).  With one wave per 64-row band holding the whole
-// N, every A row feeds exactly one wave, so staging A through LDS (tile 14) bought no reuse
+// Skinny row GEMM (N = 32 outputs: the narrow networks' level 0; RG_256x32G).  With one wave per 64-row band holding the whole
+// N, every A row feeds exactly one wave, so staging A through LDS (RG_256x32) bought no reuse
 // and held the CU to one 83-KB block of four waves.  Here every MFMA operand comes from
 // global memory straight into registers, in the layout the LDS-staged tiles read (lane half h
 // owns k = 4h..4h+3 of each 8-k group: one dwordx4 of A per accumulator row band and one of
@@ -1041,8 +1041,17 @@ using RowTile13 = RowTile<128, 32, 64, 32, 32, true, 2>;
 using RowTile14 = RowTile<256, 32, 64, 32, 32, true>;
 // (r01-r03: 256x64, 128x128 with 64-K chunks, 256x128, three waves per SIMD and
 // MFMA-phase s_setprio variants measured at or below these; not kept)
-#define ROWGEMM_TILES(X) \
-    X(0, RowTile0) X(1, RowTile1) X(4, RowTile4) X(6, RowTile6) X(13, RowTile13) X(14, RowTile14)
+#define ROWGEMM_TILES(X)                                                                      \
+    X(RG_128x128D, RowTile0) X(RG_128x64, RowTile1) X(RG_128x128, RowTile4) X(RG_128x128K64, RowTile6) \
+    X(RG_128x32, RowTile13) X(RG_256x32, RowTile14)
+// a row of tiles.h against the kernel's template type (BK: the member its label prints third)
+#define TILE_ROW_IS(TAB, BK, id, T)                                                              \
+    static_assert(find_tile(TAB, id) && find_tile(TAB, id)->bm == T::BM && find_tile(TAB, id)->bn == T::BN && \
+                      find_tile(TAB, id)->bk == T::BK, "tiles.h: row " #id " is not " #T);
+#define RG_IS(id, T) \
+    TILE_ROW_IS(ROW_TILES, BK, id, T) static_assert((find_tile(ROW_TILES, id)->kind == K_REG2) == T::DBUF, #id);
+ROWGEMM_TILES(RG_IS)
+#undef RG_IS
 
 template <int AMODE, int AOP, int EMODE, class T, bool BF>
 static int rowgemm_go(const RowGemmArgs& a, hipStream_t s) {
@@ -1057,7 +1066,7 @@ static int rowgemm_go(const RowGemmArgs& a, hipStream_t s) {
     }
 }
 
-// tile 15 = 256x32 (32-k chunks, two waves per SIMD)
+// RG_256x32G (32-k chunks, two waves per SIMD)
 template <int AMODE, int AOP, int EMODE, int NT, int GK, int OCC>
 static int rowgemm_direct_go(const RowGemmArgs& a, hipStream_t s) {
     if constexpr (AOP == OP_DZ) {
@@ -1081,55 +1090,15 @@ template <int AMODE, int AOP, int EMODE, bool BF>
 static int rowgemm_tile(const RowGemmArgs& a, int tile, hipStream_t s) {
     if constexpr (!BF) {
         // (r04 A/B, not kept: 16-k chunks at four waves per SIMD for 32 outputs, and the
-        // same kernel for 64 / 96 outputs -- slower / neutral against tiles 19/25 and 15)
-        if (tile == 15) return rowgemm_direct_go<AMODE, AOP, EMODE, 1, 4, 2>(a, s);
+        // same kernel for 64 / 96 outputs -- slower / neutral against RG_P128x64 / RG_P3_128x64 and RG_256x32G)
+        static_assert(row_desc(RG_256x32G)->bm == 256 && row_desc(RG_256x32G)->bn == 32 * 1, "tiles.h");
+        if (tile == RG_256x32G) return rowgemm_direct_go<AMODE, AOP, EMODE, 1, 4, 2>(a, s);
     }
 #define RG_CASE(id, T) \
     if (tile == id) return rowgemm_go<AMODE, AOP, EMODE, T, BF>(a, s);
     ROWGEMM_TILES(RG_CASE)
 #undef RG_CASE
     return -1;
-}
-
-int rowgemm_tile_dims(int tile, int* bm, int* bn, int* bk) {
-    if (tile == 15) {  // rowgemm_direct_kernel (operands straight from global memory)
-        *bm = 256;
-        *bn = 32;
-        *bk = 32;
-        return 0;
-    }
-    if (tile == 18 || tile == 19) {  // rowgemm_pipe_kernel (loads two chunks ahead)
-        *bm = 128;
-        *bn = tile % 2 == 0 ? 128 : 64;
-        *bk = 32;
-        return 0;
-    }
-    if (tile == 25 || tile == 26) {  // rowgemm_pipe_kernel 128x64, three blocks per CU
-        *bm = 128;
-        *bn = 64;
-        *bk = 32;
-        return 0;
-    }
-#define RG_DIMS(id, T)   \
-    if (tile == id) {    \
-        *bm = T::BM;     \
-        *bn = T::BN;     \
-        *bk = T::BK;     \
-        return 0;        \
-    }
-    ROWGEMM_TILES(RG_DIMS)
-#undef RG_DIMS
-    return -1;
-}
-
-int rowgemm_tile_dbuf(int tile) {
-    if (tile == 15) return 3;  // operands straight from global memory
-    if (tile == 18 || tile == 19 || tile == 25 || tile == 26) return 2;  // pipelined
-#define RG_DB(id, T) \
-    if (tile == id) return T::DBUF ? 1 : 0;
-    ROWGEMM_TILES(RG_DB)
-#undef RG_DB
-    return 0;
 }
 
 // BF (bf16 MFMA) is instantiated for the combinations of the BN -> ReLU network
@@ -1181,12 +1150,11 @@ int launch_rowgemm(const RowGemmArgs& a, int tile, hipStream_t s) {
     if ((a.escale != nullptr) != (a.eshift != nullptr) || (a.arelu && !aff)) return -1;
     if (a.emode == E_RESID && !a.escale) return -1;
     if ((a.bt != nullptr) == (a.bt16 != nullptr)) return -1;  // exactly one weight image
-    // ids 18, 19, 25, 26: the software-pipelined f32 kernel (128x128 / 128x64 loading two chunks
-    // ahead; 25 / 26: 128x64 at three blocks per CU); operands it does not take (bf16 weights,
-    // > 2 GB offsets) run the same tile shape on the register-staged kernel
-    if (tile == 18 || tile == 19 || tile == 25 || tile == 26) {
-        if (rowgemm_pipe_ok(a)) return launch_rowgemm_pipe(a, tile <= 19 ? tile - 16 : tile - 21, s);
-        tile = tile == 18 ? 4 : 1;
+    // the software-pipelined f32 kernel; operands it does not take (bf16 weights, > 2 GB offsets)
+    // run the same tile shape on the register-staged kernel
+    if (const Tile* t = row_desc(tile); t && t->kind == K_PIPE) {
+        if (rowgemm_pipe_ok(a)) return launch_rowgemm_pipe(a, tile, s);
+        tile = t->fallback;
     }
     return a.bt16 ? rowgemm_dispatch<true>(a, tile, s) : rowgemm_dispatch<false>(a, tile, s);
 }
@@ -1200,16 +1168,11 @@ using WgTile7 = WgTile<64, 64, 32, 32, 32, 3>;
 // 32-channel operands (narrow level 0): 64 x 32 (2 waves), 32 x 32 (1 wave)
 using WgTile8 = WgTile<64, 32, 32, 32, 32>;
 using WgTile9 = WgTile<32, 32, 32, 32, 32>;
-#define WGRAD_TILES(X) \
-    X(0, WgTile0) X(3, WgTile3) X(5, WgTile5) X(7, WgTile7) X(8, WgTile8) X(9, WgTile9)
-
-#define WG_DIMS_R3(id, T) \
-    if (tile == id) {     \
-        *bm = T::BM;      \
-        *bn = T::BN;      \
-        *bkp = T::BKP;    \
-        return 0;         \
-    }
+#define WGRAD_TILES(X)                                                                         \
+    X(WG_128x128, WgTile0) X(WG_64x128, WgTile3) X(WG_128x64, WgTile5) X(WG_64x64, WgTile7) \
+    X(WG_64x32, WgTile8) X(WG_32x32, WgTile9)
+#define WG_IS(id, T) TILE_ROW_IS(WG_TILES, BKP, id, T)
+WGRAD_TILES(WG_IS)
 // one-row-of-taps tiles (wgrad_row3_kernel, ids 20..): BM x BN per tap, 3 taps per block
 using Wr3Tile0 = WgTile<64, 64, 32, 32, 32>;    // 4 waves, 3 x 32x32 per wave
 using Wr3Tile1 = WgTile<128, 64, 64, 32, 32>;   // 4 waves, 3 x 64x32
@@ -1221,33 +1184,17 @@ using Wr3Tile5 = WgTile<64, 32, 32, 32, 32>;    // Cin 64 (a [skip | up] concat)
 using Wr3Tile6 = WgTile<32, 64, 32, 32, 32>;    // Cin 32, Cout 64
 // (r03: 64-pixel chunks, 16-pixel rows, all three tap rows per block and a software-
 // pipelined schedule of these tiles measured at or below them; not kept)
-#define WGRAD_ROW3_TILES(X) \
-    X(20, Wr3Tile0) X(21, Wr3Tile1) X(22, Wr3Tile2) X(23, Wr3Tile3) X(24, Wr3Tile4) X(25, Wr3Tile5) \
-    X(26, Wr3Tile6)
-
-// a row3 block covers three taps (its split-K partition counts them)
-int wgrad_tile_taps(int tile) { return tile >= 20 ? 3 : 1; }
-
-int wgrad_tile_dims(int tile, int* bm, int* bn, int* bkp) {
-    WGRAD_ROW3_TILES(WG_DIMS_R3)
-#define WG_DIMS(id, T) \
-    if (tile == id) {  \
-        *bm = T::BM;   \
-        *bn = T::BN;   \
-        *bkp = T::BKP; \
-        return 0;      \
-    }
-    WGRAD_TILES(WG_DIMS)
-#undef WG_DIMS
-    return -1;
-}
+#define WGRAD_ROW3_TILES(X)                                                                       \
+    X(WG3_64x64, Wr3Tile0) X(WG3_128x64, Wr3Tile1) X(WG3_64x128, Wr3Tile2) X(WG3_128x128, Wr3Tile3) \
+    X(WG3_32x32, Wr3Tile4) X(WG3_64x32, Wr3Tile5) X(WG3_32x64, Wr3Tile6)
+WGRAD_ROW3_TILES(WG_IS)
+#undef WG_IS
 
 template <int AOP, bool BDZ>
 static int wgrad_row3_tile(const WgradArgs& a, int tile, hipStream_t s) {
 #define WR3_CASE(id, T)                                                                       \
     if (tile == id) {                                                                         \
-        if (a.Mw != 9 * a.CA || a.CA % T::BM || a.Nw % T::BN || a.CB % T::BN ||               \
-            a.pps % T::BKP || a.W % T::BKP)                                                   \
+        if (a.Mw != 9 * a.CA || a.Nw % T::BN || !wg_row3_ok(*wg_desc(id), wgrad_geom(a)))   \
             return -1;                                                                        \
         const dim3 grid(3 * (a.CA / T::BM) * (a.Nw / T::BN) * a.splits);                      \
         hipLaunchKernelGGL((wgrad_row3_kernel<AOP, BDZ, T>), grid, dim3(T::THREADS), 0, s, a); \
@@ -1279,20 +1226,11 @@ using Wg16Tile0 = WgTile<128, 128, 64, 64, 32>;
 using Wg16Tile2 = WgTile<64, 64, 32, 32, 64>;
 using Wg16Tile3 = WgTile<128, 64, 64, 32, 64>;
 using Wg16Tile4 = WgTile<64, 128, 32, 64, 64>;
-#define WGRAD16_TILES(X) X(0, Wg16Tile0) X(2, Wg16Tile2) X(3, Wg16Tile3) X(4, Wg16Tile4)
-
-int wgrad16_tile_dims(int tile, int* bm, int* bn, int* bkp) {
-#define WG16_DIMS(id, T) \
-    if (tile == id) {    \
-        *bm = T::BM;     \
-        *bn = T::BN;     \
-        *bkp = T::BKP;   \
-        return 0;        \
-    }
-    WGRAD16_TILES(WG16_DIMS)
-#undef WG16_DIMS
-    return -1;
-}
+#define WGRAD16_TILES(X) \
+    X(WGB_128x128, Wg16Tile0) X(WGB_64x64, Wg16Tile2) X(WGB_128x64, Wg16Tile3) X(WGB_64x128, Wg16Tile4)
+#define WGB_IS(id, T) TILE_ROW_IS(WGB_TILES, BKP, id, T)
+WGRAD16_TILES(WGB_IS)
+#undef WGB_IS
 
 #define WG16_CASE(id, T)                                                                      \
     if (tile == id) {                                                                         \
@@ -1330,8 +1268,7 @@ int launch_wgrad(const WgradArgs& a, int tile, hipStream_t s) {
     const bool aff = a.ascale != nullptr, dz = a.bcoef != nullptr;
     if (a.arelu && !aff) return -1;
     if (a.arelu && dz && !a.bdznomask) return -1;  // BN -> ReLU A' operands come with an unmasked dz
-    if (tile >= 20) {  // one row of 3x3 taps per block (wgrad_row3_kernel)
-        if (a.amode != G_CONV3 || a.bmode != G_IDENT) return -1;
+    if (const Tile* t = wg_desc(tile); t && t->taps == 3) {  // wgrad_row3_kernel
         if (dz && a.arelu) return wgrad_row3_tile<OP_AFFINE_RELU, true>(a, tile, s);
         if (dz) return aff ? wgrad_row3_tile<OP_AFFINE, true>(a, tile, s)
                            : wgrad_row3_tile<OP_PLAIN, true>(a, tile, s);

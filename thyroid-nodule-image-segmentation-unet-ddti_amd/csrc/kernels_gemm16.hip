@@ -207,7 +207,7 @@ __global__ __launch_bounds__(T::THREADS, T::OCC) void rowgemm16_kernel(RowGemmAr
 }
 
 // ------------------------------------------------------------------------------------
-// Tap-row halo variant of the 3x3 conv GEMM (tile 19, G_CONV3 only, W >= 16).  The
+// Tap-row halo variant of the 3x3 conv GEMM (R16_H256x256, G_CONV3 only, W >= 16).  The
 // one-tap kernel restages the block's 256 A rows for each of the 9 taps; here a stage holds
 // the HALO of one tap row dy -- the block's image rows shifted by dy - 1, one extra pixel
 // either side (ROWS x (SEG + 2) rows, <= 288) -- with the B rows of the three taps (dy, 0..2),
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(T::THREADS, T::OCC) void rowgemm16_kernel(RowGemmAr
 //   K order: dy, 32-channel slice, dx, k -- a reordering of the one-tap kernel's sum, so
 //   results agree with the other tiles to fp32 rounding, not bitwise.
 // ------------------------------------------------------------------------------------
-// BM x BN block tiles: 256 x 256 (tile 19) and 512 x 128 (tile 20, the 128-output layers of
+// BM x BN block tiles: 256 x 256 (R16_H256x256) and 512 x 128 (R16_H512x128, the 128-output layers of
 // config 4's level 0: 8 waves of 128 x 64 either way).
 // (r05, removed in r06: waves 4..7 running each stage's last tap after the next barrier, with
 // and without the next DMA behind the first tap's reads; the same kernel on 16x16x32 MFMAs:
@@ -359,25 +359,29 @@ __global__ __launch_bounds__(512, 1) void rowgemm16_row3_kernel(RowGemmArgs p) {
 }
 
 template <int EMODE, int BM, int BN>
-static int rg16r3_go(const RowGemmArgs& a, hipStream_t s) {
-    // BM % W == 0 or W % BM == 0 keeps a tile on whole rows / row segments; W >= 16 bounds the halo
-    if (a.amode != G_CONV3 || a.N % BN || a.C % 32 || a.K != 9 * a.C) return -1;
-    if (a.W < 16 || (BM % a.W && a.W % BM)) return -1;
+static int rg16r3_go(const RowGemmArgs& a, const Tile& t, hipStream_t s) {
+    if (t.bm != BM || t.bn != BN) return -1;
+    if (!halo_ok(t, row_geom(a)) || a.N % BN || a.C % 32 || a.K != 9 * a.C) return -1;
     const dim3 grid(((a.M + BM - 1) / BM) * (a.N / BN));
     hipLaunchKernelGGL((rowgemm16_row3_kernel<EMODE, BM, BN>), grid, dim3(512), 0, s, a);
     return (int)hipGetLastError();
 }
 
-// tiles: 0 = 128x128, 2 stages (64 KB LDS, 2 blocks/CU); 2 = 256x128, 8 waves, 2 stages
-// (96 KB); 4 = 256x256, 8 waves of 128x64, 2 stages (128 KB); 6 = 512x128, 8 waves of 128x64,
-// 2 stages (160 KB); 19 / 20 = the tap-row halo kernel at 256x256 / 512x128
+// (RG16_TILES of tiles.h; the halo tiles run rowgemm16_row3_kernel)
 using T16_0 = Tile16<128, 128, 64, 64, 2, 2>;
 using T16_2 = Tile16<256, 128, 64, 64, 2, 1>;
 using T16_4 = Tile16<256, 256, 128, 64, 2, 1>;
 using T16_6 = Tile16<512, 128, 128, 64, 2, 1>;
 // (r06, not kept: 128x128 with three / four stages at one block per CU for the deep levels' small
 // grids, config 4 -1.2 %, profiles/r06_c4_ab.txt)
-#define ROWGEMM16_TILES(X) X(0, T16_0) X(2, T16_2) X(4, T16_4) X(6, T16_6)
+#define ROWGEMM16_TILES(X) X(R16_128x128, T16_0) X(R16_256x128, T16_2) X(R16_256x256, T16_4) X(R16_512x128, T16_6)
+#define TILE16_IS(TAB, id, T)                                                                     \
+    static_assert(find_tile(TAB, id) && find_tile(TAB, id)->bm == T::BM && find_tile(TAB, id)->bn == T::BN && \
+                      find_tile(TAB, id)->bk == T::S && find_tile(TAB, id)->per_cu == T::OCC,      \
+                  "tiles.h: row " #id " is not " #T);
+#define RG16_IS(id, T) TILE16_IS(RG16_TILES, id, T)
+ROWGEMM16_TILES(RG16_IS)
+#undef RG16_IS
 
 template <int AMODE, int EMODE, class T>
 static int rg16_go(const RowGemmArgs& a, hipStream_t s) {
@@ -391,14 +395,13 @@ static int rg16_go(const RowGemmArgs& a, hipStream_t s) {
 template <int AMODE, int EMODE>
 static int rg16_tile(const RowGemmArgs& a0, int tile, hipStream_t s) {
     RowGemmArgs a = a0;
-    if (a.tgm < 0) {  // tile order: the group size for this tile's grid (two blocks per CU on tile 0)
-        int bm = 0, bn = 0;
-        if (rowgemm16_tile_dims(tile, &bm, &bn, nullptr) != 0) return -1;
-        a.tgm = tile_group_auto(a.M, a.N, bm, bn, tile == 0 ? 64 : 32);
-    }
-    if (tile == 19 || tile == 20) {
+    const Tile* t = rg16_desc(tile);
+    if (!t) return -1;
+    // tile order: the group size for this tile's grid (32 CUs per XCD)
+    if (a.tgm < 0) a.tgm = tile_group_auto(a.M, a.N, t->bm, t->bn, 32 * t->per_cu);
+    if (t->kind == K_HALO) {
         if constexpr (AMODE == G_CONV3)
-            return tile == 19 ? rg16r3_go<EMODE, 256, 256>(a, s) : rg16r3_go<EMODE, 512, 128>(a, s);
+            return tile == R16_H256x256 ? rg16r3_go<EMODE, 256, 256>(a, *t, s) : rg16r3_go<EMODE, 512, 128>(a, *t, s);
         return -1;
     }
 #define RG16_CASE(id, T) \
@@ -1053,12 +1056,13 @@ __global__ __launch_bounds__(512, 1) void wgrad16_row3_m16_kernel(WgradArgs p) {
                 }
 }
 
-// wgrad16 tiles: 0 = 128x128, 64 pixels per stage, 2 stages (64 KB, 2 blocks/CU);
-// 2 = 256x256, 8 waves of 128x64, 2 stages (128 KB, 1 block/CU)
-// (r01-r02, not kept: 3-stage 128x128, 256x128 / 128x256 at 3 stages)
+// (WG16_TILES of tiles.h; r01-r02, not kept: 3-stage 128x128, 256x128 / 128x256 at 3 stages)
 using W16_0 = WTile16<128, 128, 64, 64, 64, 2, 2>;
 using W16_2 = WTile16<256, 256, 128, 64, 64, 2, 1>;
-#define WGRAD16G_TILES(X) X(0, W16_0) X(2, W16_2)
+#define WGRAD16G_TILES(X) X(W16_128x128, W16_0) X(W16_256x256, W16_2)
+#define WG16_IS(id, T) TILE16_IS(WG16_TILES, id, T)
+WGRAD16G_TILES(WG16_IS)
+#undef WG16_IS
 
 template <int AMODE, int BMODE, class T>
 static int wg16_go(const WgradArgs& a, hipStream_t s) {
@@ -1069,43 +1073,6 @@ static int wg16_go(const WgradArgs& a, hipStream_t s) {
 }
 
 }  // namespace
-
-int wgrad16g_tile_dims(int tile, int* bm, int* bn, int* stages) {
-    if (tile == 4 || tile == 7) {  // tap-row: 128 x 128 per tap, three taps per block, 4 stages
-        *bm = *bn = 128;
-        if (stages) *stages = 4;
-        return 0;
-    }
-#define WG16_DIMS(id, T)          \
-    if (tile == id) {             \
-        *bm = T::BM;              \
-        *bn = T::BN;              \
-        if (stages) *stages = T::S; \
-        return 0;                 \
-    }
-    WGRAD16G_TILES(WG16_DIMS)
-#undef WG16_DIMS
-    return -1;
-}
-
-int rowgemm16_tile_dims(int tile, int* bm, int* bn, int* stages) {
-    if (tile == 19 || tile == 20) {  // tap-row halo 256x256 / 512x128
-        *bm = tile == 19 ? 256 : 512;
-        *bn = tile == 19 ? 256 : 128;
-        if (stages) *stages = 2;
-        return 0;
-    }
-#define RG16_DIMS(id, T)          \
-    if (tile == id) {             \
-        *bm = T::BM;              \
-        *bn = T::BN;              \
-        if (stages) *stages = T::S; \
-        return 0;                 \
-    }
-    ROWGEMM16_TILES(RG16_DIMS)
-#undef RG16_DIMS
-    return -1;
-}
 
 // The combinations of the BN -> ReLU network (models/mod.py): conv forward (E_STATS),
 // conv dgrad (E_STORE / E_STORE_BN), ConvT forward (E_CONVT), ConvT dgrad (G_UP2, E_STORE_BN);
@@ -1137,19 +1104,17 @@ int launch_rowgemm16(const RowGemmArgs& a, int tile, hipStream_t s) {
 // skip (A', B' G_IDENT: a plain product over pixels); no bias column sums.
 int launch_wgrad16(const WgradArgs& a, int tile, hipStream_t s) {
     if (a.aoff || a.boff || a.ascale || a.bcoef || a.bias_slab || !a.zero16 || a.P < 1) return -1;
-    if (tile == 4 || tile == 7) {  // tap-row kernel: 3x3 conv layers, W % 64 == 0 (4: 32x32x16, 4 LDS
-                                   // stages; 7: 16x16x32 with the re-read stagger, r06, and also
-                                   // W = 32 / 16 with H W % 64 == 0)
-        const bool deep = tile == 7 && (a.W == 32 || a.W == 16) && (a.H * a.W) % 64 == 0;
-        if (a.amode != G_CONV3 || a.bmode != G_IDENT || a.Mw != 9 * a.CA || a.Nw != a.CB ||
-            a.CA % 128 || a.CB % 128 || (a.W % 64 && !deep) || a.pps % 64 || a.P % 64)
-            return -1;
+    const Tile* t = wg16_desc(tile);
+    if (t && t->taps == 3) {  // tap-row kernels: 3x3 conv layers (128 x 128 per tap, 4 LDS stages)
+        static_assert(wg16_desc(W16_R3)->bk == 4 && wg16_desc(W16_R3M)->bk == 4, "tiles.h: stages");
+        if (a.Mw != 9 * a.CA || a.Nw != a.CB || !wg16_row3_ok(*t, wgrad_geom(a))) return -1;
         const dim3 grid((a.CA / 128) * 3 * (a.Nw / 128) * a.splits);
-        if (tile == 7 && a.W == 32)
+        const bool m16 = t->kind == K_TAPROW_M16;
+        if (m16 && a.W == 32)
             hipLaunchKernelGGL((wgrad16_row3_m16_kernel<4, true, 32>), grid, dim3(512), 0, s, a);
-        else if (tile == 7 && a.W == 16)
+        else if (m16 && a.W == 16)
             hipLaunchKernelGGL((wgrad16_row3_m16_kernel<4, true, 16>), grid, dim3(512), 0, s, a);
-        else if (tile == 7)
+        else if (m16)
             hipLaunchKernelGGL((wgrad16_row3_m16_kernel<4, true>), grid, dim3(512), 0, s, a);
         else
             hipLaunchKernelGGL((wgrad16_row3_kernel<4>), grid, dim3(512), 0, s, a);
@@ -1157,8 +1122,8 @@ int launch_wgrad16(const WgradArgs& a, int tile, hipStream_t s) {
     }
 #define WG16G(AM, BMD)                                   \
     do {                                                 \
-        if (tile == 0) return wg16_go<AM, BMD, W16_0>(a, s); \
-        if (tile == 2) return wg16_go<AM, BMD, W16_2>(a, s); \
+        if (tile == W16_128x128) return wg16_go<AM, BMD, W16_0>(a, s); \
+        if (tile == W16_256x256) return wg16_go<AM, BMD, W16_2>(a, s); \
         return -1;                                       \
     } while (0)
     if (a.amode == G_CONV3 && a.bmode == G_IDENT) WG16G(G_CONV3, G_IDENT);

@@ -326,10 +326,15 @@ static int pipe_go(const RowGemmArgs& a, hipStream_t s) {
 
 template <int AMODE, int AOP, int EMODE>
 static int pipe_tile(const RowGemmArgs& a, int tile, hipStream_t s) {
-    if (tile == 2) return pipe_go<AMODE, AOP, EMODE, PipeTile2>(a, s);
-    if (tile == 3) return pipe_go<AMODE, AOP, EMODE, PipeTile3>(a, s);
-    if (tile == 4) return pipe_go<AMODE, AOP, EMODE, PipeTile4>(a, s);
-    if (tile == 5) return pipe_go<AMODE, AOP, EMODE, PipeTile5>(a, s);
+#define PIPE_CASE(id, T)                                                                    \
+    static_assert(row_desc(id)->kind == K_PIPE && row_desc(id)->bm == T::BM && row_desc(id)->bn == T::BN && \
+                      row_desc(id)->bk == T::BK, "tiles.h: row " #id " is not " #T);           \
+    if (tile == id) return pipe_go<AMODE, AOP, EMODE, T>(a, s);
+    PIPE_CASE(RG_P128x128, PipeTile2)
+    PIPE_CASE(RG_P128x64, PipeTile3)
+    PIPE_CASE(RG_P3_128x64, PipeTile4)
+    PIPE_CASE(RG_P3_128x64A, PipeTile5)
+#undef PIPE_CASE
     return -1;
 }
 
@@ -345,8 +350,7 @@ int rowgemm_pipe_ok(const RowGemmArgs& a) {
     return 1;
 }
 
-// tile: 2 = 128x128, 3 = 128x64 (loading two chunks ahead), 4 / 5 = 128x64 at three blocks per
-// CU (one / two chunks ahead)
+// tile: a K_PIPE id of ROW_TILES
 int launch_rowgemm_pipe(const RowGemmArgs& a, int tile, hipStream_t s) {
     if (!rowgemm_pipe_ok(a) || a.M < 1 || a.K != gather_taps(a.amode) * a.C) return -1;
     const bool aff = a.ascale != nullptr;

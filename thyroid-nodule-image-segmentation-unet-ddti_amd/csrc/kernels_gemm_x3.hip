@@ -530,23 +530,24 @@ __global__ __launch_bounds__(BM / 64 * 2 * 64, BM == 256 ? 1 : 2) void rowgemm_x
 }
 
 template <int EMODE, int BN, int BM = 256>
-static int x3r3_go(const RowGemmArgs& a, hipStream_t s) {
-    // BM % W == 0 or W % BM == 0 keeps a tile on whole rows / row segments; W >= 16 bounds the halo
-    if (a.amode != G_CONV3 || a.N % BN || a.C % 32 || a.K != 9 * a.C) return -1;
-    if (a.W < 16 || (BM % a.W && a.W % BM)) return -1;
+static int x3r3_go(const RowGemmArgs& a, const Tile& t, hipStream_t s) {
+    if (t.bm != BM || t.bn != BN || !halo_ok(t, row_geom(a)) || a.N % BN || a.C % 32 || a.K != 9 * a.C) return -1;
     const dim3 grid(((a.M + BM - 1) / BM) * (a.N / BN));
     hipLaunchKernelGGL((rowgemm_x3_row3_kernel<EMODE, BN, BM>), grid, dim3(BM / 64 * 2 * 64), 0, s, a);
     return (int)hipGetLastError();
 }
-// tiles (split accumulators; probe: profiles/r04_x3_probe_*.txt): 0 = 256x128 (8 waves of
-// 64x64, 2 stages, 144 KB, one block per CU), 1 = 128x128 (4 waves, 2 stages: grids below 256
-// blocks of tile 0), 2 = 128x64 (4 waves of 64x32, two blocks per CU: the 64-output layers),
-// 3 = 256x64 (8 waves of 64x32, B region padded to 16 KB)
+// X3_TILES of tiles.h (split accumulators; probe: profiles/r04_x3_probe_*.txt; 256x64: B region
+// padded to 16 KB)
 using TX0 = TileX3<256, 128, 64, 64, 2, 1, 1>;
 using TX1 = TileX3<128, 128, 64, 64, 2, 1, 1>;
 using TX2 = TileX3<128, 64, 64, 32, 2, 2, 1>;
 using TX3 = TileX3<256, 64, 64, 32, 2, 1, 1>;
-#define ROWGEMM_X3_TILES(X) X(0, TX0) X(1, TX1) X(2, TX2) X(3, TX3)
+#define ROWGEMM_X3_TILES(X) X(X3_256x128, TX0) X(X3_128x128, TX1) X(X3_128x64, TX2) X(X3_256x64, TX3)
+#define X3_IS(id, T)                                                                              \
+    static_assert(x3_desc(id)->bm == T::BM && x3_desc(id)->bn == T::BN && x3_desc(id)->bk == T::BK && \
+                      x3_desc(id)->per_cu == T::OCC, "tiles.h: row " #id " is not " #T);
+ROWGEMM_X3_TILES(X3_IS)
+#undef X3_IS
 
 template <int AMODE, int EMODE, class T>
 static int x3_go(const RowGemmArgs& a, hipStream_t s) {
@@ -560,12 +561,11 @@ static int x3_go(const RowGemmArgs& a, hipStream_t s) {
 template <int AMODE, int EMODE>
 static int x3_tile(const RowGemmArgs& a0, int tile, hipStream_t s) {
     RowGemmArgs a = a0;
-    if (a.tgm < 0) {  // tile order: the group size for this tile's grid (two blocks per CU on 128 x 64)
-        int bm = 0, bn = 0;
-        if (rowgemm_x3_tile_dims(tile, &bm, &bn) != 0) return -1;
-        a.tgm = tile_group_auto(a.M, a.N, bm, bn, (tile == 2 || tile == 6) ? 64 : 32);
-    }
-    if (tile == 4 || tile == 6) {  // tap-row halo kernel (3x3 convs): 256 x 128 / 128 x 64
+    const Tile* t = x3_desc(tile);
+    if (!t) return -1;
+    // tile order: the group size for this tile's grid (32 CUs per XCD)
+    if (a.tgm < 0) a.tgm = tile_group_auto(a.M, a.N, t->bm, t->bn, 32 * t->per_cu);
+    if (t->kind == K_HALO) {  // tap-row halo kernel (3x3 convs): 256 x 128 / 128 x 64
         // (r04, not kept: 4-wave 128x64 / 64x128 wave tiles, within noise of 8 waves; B
         // straight from global memory into registers instead of the LDS ring, one barrier per
         // halo group, bit-identical but 222 -> 161 TF/s: the per-wave B loads cost more than
@@ -573,7 +573,7 @@ static int x3_tile(const RowGemmArgs& a0, int tile, hipStream_t s) {
         // 256 x 64 with a three-slot B ring, B two sub-steps ahead: bit-identical, no gain;
         // r05: 256 x 64 on 8 waves, 0.2 % slower than 128 x 64, removed in r06)
         if constexpr (AMODE == G_CONV3)
-            return tile == 4 ? x3r3_go<EMODE, 128>(a, s) : x3r3_go<EMODE, 64, 128>(a, s);
+            return tile == X3_H256x128 ? x3r3_go<EMODE, 128>(a, *t, s) : x3r3_go<EMODE, 64, 128>(a, *t, s);
         return -1;
     }
     // (r05, removed in r06: the one-tap tiles on 16x16x32, config 2 within noise,
@@ -1113,7 +1113,9 @@ __global__ __launch_bounds__((BM / 32) * (BN / 32) * 64, OCC) void wgrad_x3_row3
 // three LDS stages of 32 pixels
 using WX0 = WTileX3<128, 128, 64, 32, 3, 1>;
 using WX1 = WTileX3<64, 64, 32, 32, 3, 1>;
-#define WGRAD_X3_TILES(X) X(0, WX0) X(1, WX1)
+static_assert(wx3_desc(WX3_128x128)->bm == WX0::BM && wx3_desc(WX3_128x128)->bn == WX0::BN &&
+                  wx3_desc(WX3_64x64)->bm == WX1::BM && wx3_desc(WX3_64x64)->bn == WX1::BN &&
+                  wx3_desc(WX3_128x128)->bk == WX0::BKP, "tiles.h: WX3_TILES");
 
 template <int AMODE, int BMODE, class T>
 static int wx3_go(const WgradArgs& a, hipStream_t s) {
@@ -1272,23 +1274,6 @@ __global__ __launch_bounds__(256) void bn_dz_x3_kernel(const float* __restrict__
 
 }  // namespace
 
-int rowgemm_x3_tile_dims(int tile, int* bm, int* bn) {
-    if (tile == 4 || tile == 6) {  // tap-row halo 256 x 128 / 128 x 64
-        *bm = tile == 6 ? 128 : 256;
-        *bn = tile == 4 ? 128 : 64;
-        return 0;
-    }
-#define X3_DIMS(id, T)  \
-    if (tile == id) {   \
-        *bm = T::BM;    \
-        *bn = T::BN;    \
-        return 0;       \
-    }
-    ROWGEMM_X3_TILES(X3_DIMS)
-#undef X3_DIMS
-    return -1;
-}
-
 // A: x3 image (a16, lda channels per row, channel offset aoff), Bt: x3 weights [N][K]
 int launch_rowgemm_x3(const RowGemmArgs& a, int tile, hipStream_t s) {
     if (!a.a16 || !a.bt16 || !a.zero16 || a.M < 1 || a.K != gather_taps(a.amode) * a.C) return -1;
@@ -1321,27 +1306,8 @@ int k_to_x3(const float* src, int ld, int off, int C, const float* scale, const 
     return (int)hipGetLastError();
 }
 
-// tap-row tiles (BM ci x BN co per tap, three taps per block): 2 = 64x128, 4 = 64x64 (r05-r06
-// tile 3, 128x64, measured 20 % slower than 4 on config 2's 128 -> 64 conv and was removed)
-static const int WX3R3_DIMS[5][2] = {{0, 0}, {0, 0}, {64, 128}, {0, 0}, {64, 64}};
-
-int wgrad_x3_tile_dims(int tile, int* bm, int* bn) {
-    if (tile == 2 || tile == 4) {
-        *bm = WX3R3_DIMS[tile][0];
-        *bn = WX3R3_DIMS[tile][1];
-        return 0;
-    }
-#define WX3_DIMS(id, T) \
-    if (tile == id) {   \
-        *bm = T::BM;    \
-        *bn = T::BN;    \
-        return 0;       \
-    }
-    WGRAD_X3_TILES(WX3_DIMS)
-#undef WX3_DIMS
-    return -1;
-}
-
+// (tap-row tiles: r05-r06 tile 3, 128x64, measured 20 % slower than 64x64 on config 2's 128 -> 64
+// conv and was removed)
 // Weight gradient from x3 images: a / b point at uint16 x3 images (lda / ldb channels per
 // row, channel offsets aoff / boff multiples of 32), zero16 at a zeroed page.  3x3 conv (A'
 // G_CONV3, B' G_IDENT) and ConvT (A' G_IDENT, B' G_UP2); no bias column sums.
@@ -1350,18 +1316,17 @@ int wgrad_x3_tile_dims(int tile, int* bm, int* bn) {
 int launch_wgrad_x3(const WgradArgs& a, int tile, hipStream_t s) {
     if (a.ascale || a.bcoef || a.bias_slab || !a.zero16 || a.P < 1) return -1;
     if (a.aoff % 32 || a.boff % 32 || a.lda % 32 || a.ldb % 32) return -1;
-    if (tile == 2 || tile == 4) {  // tap-row kernel: 3x3 convs, W % 32 == 0 or W = 16 with an even H
-        int bm = 0, bn = 0;
-        wgrad_x3_tile_dims(tile, &bm, &bn);
-        const bool w16 = a.W == 16 && a.H % 2 == 0;
-        if (a.amode != G_CONV3 || a.bmode != G_IDENT || a.Mw != 9 * a.CA || a.Nw != a.CB ||
-            a.CA % bm || a.CB % bn || (a.W % 32 && !w16) || a.pps % 32 || a.P % 32)
-            return -1;
-        const dim3 grid((a.CA / bm) * 3 * (a.CB / bn) * a.splits);
+    const Tile* t = wx3_desc(tile);
+    if (t && t->taps == 3) {  // tap-row kernel: 3x3 convs
+        static_assert(wx3_desc(WX3_R3_64x128)->bm == 64 && wx3_desc(WX3_R3_64x128)->bn == 128 &&
+                          wx3_desc(WX3_R3_64x64)->bm == 64 && wx3_desc(WX3_R3_64x64)->bn == 64, "tiles.h");
+        if (a.Mw != 9 * a.CA || a.Nw != a.CB || !wx3_row3_ok(*t, wgrad_geom(a))) return -1;
+        const bool w16 = a.W == 16;
+        const dim3 grid((a.CA / t->bm) * 3 * (a.CB / t->bn) * a.splits);
         // 64 x 128: four stages with the stagger (r05 schedule 10); 64 x 64 without it
-        if (tile == 2 && w16)
+        if (tile == WX3_R3_64x128 && w16)
             hipLaunchKernelGGL((wgrad_x3_row3_kernel<64, 128, 4, 1, true, true>), grid, dim3(512), 0, s, a);
-        else if (tile == 2)
+        else if (tile == WX3_R3_64x128)
             hipLaunchKernelGGL((wgrad_x3_row3_kernel<64, 128, 4, 1, true>), grid, dim3(512), 0, s, a);
         else if (w16)  // 64 x 64: four waves, two LDS stages, two blocks per CU
             hipLaunchKernelGGL((wgrad_x3_row3_kernel<64, 64, 2, 2, false, true>), grid, dim3(256), 0, s, a);
@@ -1371,8 +1336,8 @@ int launch_wgrad_x3(const WgradArgs& a, int tile, hipStream_t s) {
     }
 #define WX3G(AM, BMD)                                        \
     do {                                                     \
-        if (tile == 0) return wx3_go<AM, BMD, WX0>(a, s);    \
-        if (tile == 1) return wx3_go<AM, BMD, WX1>(a, s);    \
+        if (tile == WX3_128x128) return wx3_go<AM, BMD, WX0>(a, s); \
+        if (tile == WX3_64x64) return wx3_go<AM, BMD, WX1>(a, s);   \
         return -1;                                           \
     } while (0)
     if (a.amode == G_CONV3 && a.bmode == G_IDENT) WX3G(G_CONV3, G_IDENT);

@@ -334,6 +334,19 @@ void build_graph(unet_ctx* c) {
 // decided once per plan by make_routes (below, after the rules it applies); make_plan sizes
 // the workspace from it, forward_impl and backward_impl only read it.
 // ------------------------------------------------------------------------------------
+// one row GEMM as the plan fixes it (tiles.h; t is never null: NO_TILE where an option names none)
+struct GemmPlan {
+    RowGeom g{};
+    const Tile* t = &NO_TILE;
+};
+// a weight gradient's tile (t16: the LDS-DMA tile where the family is FAM_DMA16, which keeps the
+// register-staged tile's partition) and split-K partition
+struct WgradCfg {
+    const Tile* t = &NO_TILE;
+    const Tile* t16 = &NO_TILE;
+    int splits = 1, pps = 0;
+};
+
 enum Family : uint8_t {
     FAM_NONE,   // not a GEMM: the single-input-channel first conv / first skip (k_conv_first_*,
                 // k_res_first_*)
@@ -359,6 +372,12 @@ struct Route {
     Writer up = W_PREP, skip = W_PREP;
     bool head_fuse = false;   // the last conv's dz pass recomputes `do` from the 1x1 head
     bool pool_fuse = false;   // an encoder's second conv: ... from the max-pool backward's inputs
+    // chosen by plan_tiles, after the families: the forward and input-gradient GEMMs (geometry with
+    // the epilogue the block structure gives it, and tile), the weight gradient's tile and split-K
+    // partition, and whether that kernel's B' loader forms the BN-backward dz (option dz_in_wgrad)
+    GemmPlan f, d;
+    WgradCfg w;
+    bool dzw = false;
 };
 // (fixed arrays: a plan is made four times per training step, and unet_adamw_repack reads `x3`
 // from a record of its own, so building one allocates nothing)
@@ -443,65 +462,65 @@ struct Bump {
     }
 };
 
-struct WgradCfg {
-    int tile, bm, bn, bkp, splits, pps;
-};
-
-// wgrad tile (kernels_gemm.hip WGRAD_TILES) + split-K over pixels so that every layer
+// wgrad tile (tiles.h WG_TILES / WGB_TILES) + split-K over pixels so that every layer
 // launches >= 2048 blocks; options wgrad_tile_{w,n} override (tuning runs).
-// row_w: row width of a 3x3 conv's pixel grid (0 otherwise).  3x3 weight gradients on
-// rows that are a multiple of 32 pixels take the one-row-of-taps tiles (ids 20..,
-// wgrad_row3_kernel) when option wgrad_row3 selects them: 1 = every eligible layer,
+// 3x3 weight gradients on rows that are a multiple of 32 pixels take the one-row-of-taps tiles
+// (WG3_*, wgrad_row3_kernel) when option wgrad_row3 selects them: 1 = every eligible layer,
 // 2 = only layers with a 64-channel operand (the 256x256 / 128x128 levels), 0 = never.
 // The split-K partition follows from the (default) tile dims; the bf16 LDS-DMA weight
 // gradient (wg16_tile) reuses the register-staged tile's partition, so its tile choice
 // never changes the summation order.
-WgradCfg wgrad_cfg(const unet_ctx* c, int CA, int tapsA, int CB, int tapsB, int64_t P, bool bf16,
-                   int row_w = 0) {
-    const int r3 = c->opt.wgrad_row3, r3t = c->opt.wgrad_row3_tile;
-    const int tw = c->opt.wgrad_tile_w, tn = c->opt.wgrad_tile_n;
-    WgradCfg w;
-    if (bf16) {  // kernels_gemm.hip WGRAD16_TILES
-        w.tile = (CA % 128 == 0 && CB % 128 == 0) ? 0 : CA % 128 == 0 ? 3 : CB % 128 == 0 ? 4 : 2;
-        wgrad16_tile_dims(w.tile, &w.bm, &w.bn, &w.bkp);
+WgradCfg wgrad_cfg(const unet_ctx* c, const WgGeom& g, bool bf16) {
+    const Options& o = c->opt;
+    const int CA = g.CA, CB = g.CB, tapsA = gather_taps(g.amode), tapsB = gather_taps(g.bmode);
+    const int64_t P = g.P;
+    const Tile* t;
+    if (bf16) {
+        t = wgb_desc((CA % 128 == 0 && CB % 128 == 0) ? WGB_128x128
+                     : CA % 128 == 0 ? WGB_128x64 : CB % 128 == 0 ? WGB_64x128 : WGB_64x64);
     } else {
+        int id;
         if (CA % 128 == 0 && CB % 128 == 0)
-            w.tile = tw;
-        else if (CA % 64 == 0 && CB % 64 == 0 && (CA % 128 || CB % 128) && tn >= 0)
-            w.tile = (CA % 128 == 0) ? 5 : (CB % 128 == 0 ? 3 : tn);
+            id = o.wgrad_tile_w;
+        else if (CA % 64 == 0 && CB % 64 == 0 && (CA % 128 || CB % 128) && o.wgrad_tile_n >= 0)
+            id = (CA % 128 == 0) ? WG_128x64 : (CB % 128 == 0 ? WG_64x128 : o.wgrad_tile_n);
         else if (CA % 64)  // 32-channel operands (narrow networks' level 0)
-            w.tile = 9;
+            id = WG_32x32;
         else if (CB % 64)
-            w.tile = 8;
+            id = WG_64x32;
         else
-            w.tile = 7;
-        const bool row3 = tapsA == 9 && tapsB == 1 && row_w > 0 && row_w % 32 == 0 &&
-                          CA % 32 == 0 && CB % 32 == 0 &&
-                          (r3 == 1 || (r3 == 2 && (CA == 64 || CB == 64)));
-        const bool r3n = CA % 64 || CB % 64;  // a 32-channel operand (r04 tiles 24..26)
-        if (row3 && r3n && c->opt.wgrad_row3_n32) {
-            w.tile = CA % 64 ? (CB % 64 ? 24 : 26) : 25;
+            id = WG_64x64;
+        t = wg_desc(id);
+        if (!t) t = wg_desc(WG_64x64);  // an option that names no tile (both counts divide 64 then)
+        // a row3 tile exists for this GEMM (the smallest one fits), and the option selects it
+        const bool row3 = wg_row3_ok(*wg_desc(WG3_32x32), g) &&
+                          (o.wgrad_row3 == 1 || (o.wgrad_row3 == 2 && (CA == 64 || CB == 64)));
+        const bool r3n = CA % 64 || CB % 64;  // a 32-channel operand (r04)
+        const auto row3_opt = [](int id) { const Tile* q = wg_desc(id); return q && q->taps == 3 ? q : nullptr; };
+        if (row3 && r3n && o.wgrad_row3_n32) {
+            t = wg_desc(CA % 64 ? (CB % 64 ? WG3_32x32 : WG3_32x64) : WG3_64x32);
         } else if (row3 && !r3n) {
-            w.tile = r3t >= 20 ? r3t
-                               : (CA % 128 == 0 ? (CB % 128 == 0 ? 23 : 21) : (CB % 128 == 0 ? 22 : 20));
+            const Tile* forced = row3_opt(o.wgrad_row3_tile);
+            t = forced ? forced
+                       : wg_desc(CA % 128 == 0 ? (CB % 128 == 0 ? WG3_128x128 : WG3_128x64)
+                                               : (CB % 128 == 0 ? WG3_64x128 : WG3_64x64));
             // option wgrad_row3_big: the tile of the layers whose channel counts both divide
-            // 128.  Default 128x64 (21) rather than 128x128 (23): the same GEMM time (126 TF/s)
+            // 128.  Default 128x64 rather than 128x128: the same GEMM time (126 TF/s)
             // but twice the tiles, so the 1536-block target needs half the split-K slices and
             // the slab reduction halves (r02 A/B: wgrad_reduce 1.09 -> 0.64 ms, 404 -> 408 img/s)
-            if (r3t < 20 && c->opt.wgrad_row3_big >= 20 && CA % 128 == 0 && CB % 128 == 0)
-                w.tile = c->opt.wgrad_row3_big;
+            if (!forced && row3_opt(o.wgrad_row3_big) && CA % 128 == 0 && CB % 128 == 0)
+                t = row3_opt(o.wgrad_row3_big);
         }
-        wgrad_tile_dims(w.tile, &w.bm, &w.bn, &w.bkp);
     }
-    const int64_t tiles =
-        (int64_t)(tapsA * CA / (w.bm * wgrad_tile_taps(w.tile))) * (tapsB * CB / w.bn);
+    WgradCfg w;
+    w.t = t;
+    const int64_t tiles = (int64_t)(tapsA * CA / (t->bm * t->taps)) * (tapsB * CB / t->bn);
     // blocks to launch: 2048 one-tap blocks; a row3 block does the work of three, and every
     // extra split adds a full Mw x Nw slab to write and reduce
-    const int64_t target = bf16 ? c->opt.wgrad16_blocks
-                                : (w.tile >= 20 ? c->opt.wgrad_row3_blocks : c->opt.wgrad_blocks) *
-                                      (w.tile == 24 ? 4 : (w.tile == 25 || w.tile == 26) ? 2 : 1);
+    const int64_t target =
+        bf16 ? o.wgrad16_blocks : (t->taps == 3 ? o.wgrad_row3_blocks : o.wgrad_blocks) * t->per4;
     int64_t s = (target + tiles - 1) / tiles;
-    const int64_t maxs = P / (8 * w.bkp) > 0 ? P / (8 * w.bkp) : 1;  // >= 8 chunks per split
+    const int64_t maxs = P / (8 * t->bk) > 0 ? P / (8 * t->bk) : 1;  // >= 8 chunks per split
     // (P need not be a multiple of the pixel chunk: the kernel zero-fills the tail)
     if (s > maxs) s = maxs;
     if (s < 1) s = 1;
@@ -513,10 +532,10 @@ WgradCfg wgrad_cfg(const unet_ctx* c, int CA, int tapsA, int CB, int tapsB, int6
     // blocks, and the kernel took three block durations instead of two.  Instead pick the split
     // count s minimising waves(s) x chunks per block(s) + the slab traffic of s splits (the
     // one-tap kernel, option wg16_r3 = 0, gets the same partition: bit-identical).
-    // (W = 32 / 16: the deep levels' tap-row instances, wg16_r3 = 7, r06)
-    if (bf16 && tapsA == 9 && tapsB == 1 && row_w > 0 && (row_w % 64 == 0 || row_w == 32 || row_w == 16) &&
-        CA % 128 == 0 && CB % 128 == 0 && P % 64 == 0) {
-        const int64_t t3 = (int64_t)(CA / 128) * 3 * (CB / 128);
+    // (W = 32 / 16: the deep levels' tap-row instances, W16_R3M, r06)
+    const Tile& m16 = *wg16_desc(W16_R3M);
+    if (bf16 && conv_wgrad(g) && wg16_row3_rows(m16, g.W) && CA % m16.bm == 0 && CB % m16.bn == 0 && P % 64 == 0) {
+        const int64_t t3 = (int64_t)(CA / m16.bm) * 3 * (CB / m16.bn);
         const int64_t slots = c->cus;
         double best = -1;
         for (int64_t sc = 1; sc <= maxs; ++sc) {
@@ -537,7 +556,7 @@ WgradCfg wgrad_cfg(const unet_ctx* c, int CA, int tapsA, int CB, int tapsB, int6
 // bf16 math: conv / ConvT GEMMs whose K channels are a multiple of 64 and whose N is a
 // multiple of 128 run on the LDS-DMA kernel (kernels_gemm16.hip) from a prepared bf16
 // operand image; option rg16 = 0 keeps the register-staged bf16 kernel (A/B runs),
-// rg16_tile picks its tile (kernels_gemm16.hip ROWGEMM16_TILES).
+// rg16_tile picks its tile (tiles.h RG16_TILES).
 bool rg16_on(const unet_ctx* c, int C, int N) {
     return c->bf16 && c->opt.rg16 != 0 && C % 64 == 0 && N % 128 == 0;
 }
@@ -551,34 +570,34 @@ bool rg16_on(const unet_ctx* c, int C, int N) {
 //    epilogue, while two co-resident 128x128 blocks overlap one's epilogue with the other's
 //    MFMAs (r01: level-1 dgrad 1.15 -> 0.80 ms, profiles/r01_rg16_tile_sweep.txt; default 0
 //    since the r04 one-barrier halo kernel made the 256x256 / 512x128 tiles faster overall).
-int rg16_tile(const unet_ctx* c, const RowGemmArgs& g) {
+int rg16_pick(const unet_ctx* c, const RowGeom& g) {
+    const Options& o = c->opt;
     const int cout = g.emode == E_CONVT ? g.cout : 0;
-    auto fits = [&](int t) {
-        int bm = 0, bn = 0;
-        if (rowgemm16_tile_dims(t, &bm, &bn) != 0) return false;
-        if ((t == 19 || t == 20) && (g.amode != G_CONV3 || g.W < 16 || (bm % g.W && g.W % bm)))
-            return false;
-        return g.N % bn == 0 && (cout == 0 || cout % bn == 0);
+    auto fits = [&](int id) {
+        const Tile* t = rg16_desc(id);
+        if (!t || (t->kind == K_HALO && !halo_ok(*t, g))) return false;
+        return g.N % t->bn == 0 && (cout == 0 || cout % t->bn == 0);
     };
-    if (c->opt.rg16_tile >= 0) return fits(c->opt.rg16_tile) ? c->opt.rg16_tile : 0;
-    const int t0 = 0;
-    int t4 = 4;
-    if (c->opt.rg16_r3 && fits(19)) t4 = 19;  // option rg16_r3: the tap-row halo kernel
-    if (!fits(4)) {
+    const int forced = o.rg16_tile;
+    if (forced >= 0) return fits(forced) ? forced : R16_128x128;
+    const int t0 = R16_128x128;
+    int t4 = R16_256x256;
+    if (o.rg16_r3 && fits(R16_H256x256)) t4 = R16_H256x256;  // option rg16_r3: the tap-row halo kernel
+    if (!fits(R16_256x256)) {
         // option rg16_n128: a 512-row tile for the 128-output GEMMs (halo kernel for 3x3 convs)
         // (rg16_r3 = 0 turns the halo kernel off here too: the one-tap 512x128 tile instead)
-        int tn = c->opt.rg16_n128;
-        if (tn == 20 && (!c->opt.rg16_r3 || !fits(20))) tn = 6;
+        int tn = o.rg16_n128;
+        if (tn == R16_H512x128 && (!o.rg16_r3 || !fits(R16_H512x128))) tn = R16_512x128;
         if (tn < 0 || !fits(tn)) return t0;
         if ((g.M + 511) / 512 * (g.N / 128) < 256) return t0;
-        if (g.emode == E_STORE_BN && g.K < c->opt.rg16_bn_k && !c->opt.rg16_n128_bn) return t0;
+        if (g.emode == E_STORE_BN && g.K < o.rg16_bn_k && !o.rg16_n128_bn) return t0;
         return tn;
     }
     const int64_t blocks = (g.M + 255) / 256 * (g.N / 256);
     // (r06) a grid too small for 256x256 that fills the CUs with 256x128 takes it (the 16^2
     // bottleneck's 4096-output GEMMs of config 4) instead of 128x128 at two blocks per CU
-    if (blocks < 256) return (g.M + 255) / 256 * (g.N / 128) >= 256 && fits(2) ? 2 : t0;
-    if (g.emode == E_STORE_BN && g.K < c->opt.rg16_bn_k) return t0;
+    if (blocks < 256) return (g.M + 255) / 256 * (g.N / 128) >= 256 && fits(R16_256x128) ? R16_256x128 : t0;
+    if (g.emode == E_STORE_BN && g.K < o.rg16_bn_k) return t0;
     return t4;
 }
 // 3x3 weight gradients of layers with Cin, Cout multiples of 128 on the LDS-DMA
@@ -591,12 +610,14 @@ bool wg16_on(const unet_ctx* c, int CA, int CB) {
 // XCD-contiguous block order for the LDS-DMA bf16 kernels: on by default (config 4 A/B:
 // wgrad 718 -> 766 TF/s, forward 854 -> 871, dgrad -2 %, step +2 %); option xcd16 = 0 off
 int xcd16_on(const unet_ctx* c) { return c->opt.xcd16 != 0 ? 1 : 0; }
-// tile: option wg16_tile (default 256x256, tile 2) where both channel counts allow it
-int wg16_tile(const unet_ctx* c, int CA = 128, int CB = 128) {
-    const int t = c->opt.wg16_tile;
-    int bm = 0, bn = 0;
-    if (wgrad16g_tile_dims(t, &bm, &bn) != 0 || CA % bm || CB % bn) return 0;
-    return t;
+// tile: option wg16_tile (default 256x256) where both channel counts allow it; option wg16_r3: a
+// 3x3 layer the tap-row kernel takes (three taps per block from one halo row) on it.  (The split
+// count, sized for >= 2048 128x128 tiles, gives >= 512 256x256 ones.)  g.pps: the split chosen.
+const Tile* wg16_pick(const unet_ctx* c, const WgGeom& g) {
+    const Tile* t = wg16_desc(c->opt.wg16_tile);
+    if (!t || g.CA % t->bm || g.CB % t->bn) t = wg16_desc(W16_128x128);
+    const Tile* r3 = wg16_desc(c->opt.wg16_r3);
+    return r3 && r3->taps == 3 && wg16_row3_ok(*r3, g) ? r3 : t;
 }
 // ConvT weight gradient on the LDS-DMA transposed-read kernel (A' = the forward's bf16
 // ConvT input image, B' = the bf16 image of the concat gradient's up half, G_UP2-gathered);
@@ -685,71 +706,64 @@ Routes make_routes(const unet_ctx* c, bool training, int64_t P0) {
     return r;
 }
 
-// row-GEMM tile: the tap-row halo kernel for 3x3 convs (4 = 256 x 128, one block of 8 waves per
-// CU; 6 = 128 x 64 for the 64-output GEMMs, two blocks per CU); otherwise the one-tap tiles
-// (0 = 256 x 128, 1 = 128 x 128 where the 256-row grid would leave CUs idle, 2 / 3 = 128 x 64 /
-// 256 x 64: option x3_n64)
-int x3_tile(const unet_ctx* c, const RowGemmArgs& g) {
-    auto fits = [&](int t) {
-        int bm = 0, bn = 0;
-        if (rowgemm_x3_tile_dims(t, &bm, &bn) != 0 || g.N % bn) return false;
-        return g.emode != E_CONVT || g.cout % bn == 0 || bn % g.cout == 0;
+// row-GEMM tile: the tap-row halo kernel for 3x3 convs (256 x 128, or 128 x 64 for the 64-output
+// GEMMs); otherwise the one-tap tiles (256 x 128, 128 x 128 where the 256-row grid would leave CUs
+// idle, 128 x 64 / 256 x 64: option x3_n64)
+int x3_pick(const unet_ctx* c, const RowGeom& g) {
+    auto fits = [&](int id) {
+        const Tile* t = x3_desc(id);
+        if (!t || g.N % t->bn) return false;
+        return g.emode != E_CONVT || g.cout % t->bn == 0 || t->bn % g.cout == 0;
     };
-    // the halo tiles: 3x3 convs on rows of 16 .. 256k pixels (option x3_r3)
-    const bool r3ok = g.amode == G_CONV3 && g.W >= 16 && (256 % g.W == 0 || g.W % 256 == 0);
+    // the halo tiles: 3x3 convs on rows of 16 .. 256k pixels (option x3_r3), for either tile by
+    // the 256-row one's rule (which implies the 128-row one's)
+    const bool r3ok = halo_ok(*x3_desc(X3_H256x128), g);
     const int ft = c->opt.x3_tile;
-    if (ft >= 0 && fits(ft) && (ft < 4 || r3ok)) return ft;
-    if (g.N % 128 == 0 && fits(0)) {
+    if (ft >= 0 && fits(ft) && (x3_desc(ft)->kind != K_HALO || r3ok)) return ft;
+    if (g.N % 128 == 0 && fits(X3_256x128)) {
         const int64_t blocks = (int64_t)(g.M + 255) / 256 * (g.N / 128);
-        if (blocks < 256) return 1;
-        return c->opt.x3_r3 && r3ok ? 4 : 0;
+        if (blocks < 256) return X3_128x128;
+        return c->opt.x3_r3 && r3ok ? X3_H256x128 : X3_256x128;
     }
     // 64 outputs: the 128 x 64 halo tile where the 256-row grid fills the chip (r05: 0.2 % over
     // a 256 x 64 halo tile, 1.032 vs 1.103 ms for a 512 x 64 one, profiles/r05_halo_k16.txt)
-    if (g.N % 64 == 0 && c->opt.x3_r3 && r3ok && (int64_t)(g.M + 255) / 256 >= 512) return 6;
+    if (g.N % 64 == 0 && c->opt.x3_r3 && r3ok && (int64_t)(g.M + 255) / 256 >= 512) return X3_H128x64;
     return fits(c->opt.x3_n64) ? c->opt.x3_n64 : -1;
 }
 
 // weight gradient: 128x128 tile where both channel counts allow it, else 64x64; split-K over
 // pixels so the grid has >= x3_wblocks 128x128 blocks (4x that of 64x64 ones); pixels per
 // split a multiple of 256
-// 3x3 convs on rows of a multiple of 32 pixels (row_w): the tap-row kernel (tiles 2 = 64x128,
-// 4 = 64x64 per tap, three taps per block)
-WgradCfg x3_wgrad_cfg(const unet_ctx* c, int CA, int tapsA, int CB, int tapsB, int64_t P,
-                      int row_w = 0, int row_h = 0) {
-    WgradCfg w{};
-    w.tile = (CA % 128 == 0 && CB % 128 == 0) ? 0 : 1;
-    // tap-row kernel: rows of 32k pixels, or (r05) 16-pixel rows in pairs
-    const bool w16 = row_w == 16 && row_h % 2 == 0 && CA % 64 == 0 && CB % 64 == 0;
-    const bool r3 = tapsA == 9 && tapsB == 1 && ((row_w % 32 == 0 && row_w > 0) || w16);
-    // (r06: 64 x 64 rather than 128 x 64 where only the input channels divide 128 -- config 2's
-    // 128 -> 64 level-0 conv 1.53 -> 1.24 ms, profiles/r06_c2_wtile_ab.txt; tile 3 removed)
-    if (r3 && CA % 64 == 0 && CB % 128 == 0) w.tile = 2;
-    else if (r3 && CA % 64 == 0 && CB % 64 == 0) w.tile = 4;
-    if (c->opt.x3_wtile >= 0) {
-        int bm = 0, bn = 0;
-        const int t = c->opt.x3_wtile;
-        if (wgrad_x3_tile_dims(t, &bm, &bn) == 0 && CA % bm == 0 && CB % bn == 0 && (t < 2 || r3))
-            w.tile = t;
-    }
-    wgrad_x3_tile_dims(w.tile, &w.bm, &w.bn);
-    w.bkp = 32;
-    const bool tap_row = w.tile == 2 || w.tile == 4;
-    const int64_t tiles = tap_row ? (int64_t)(CA / w.bm) * 3 * (CB / w.bn)
-                                  : (int64_t)(tapsA * CA / w.bm) * (tapsB * CB / w.bn);
+// 3x3 convs the tap-row kernel takes (wx3_row3_ok): 64x128 or 64x64 per tap, three taps per block
+// (r06: 64 x 64 rather than 128 x 64 where only the input channels divide 128 -- config 2's
+// 128 -> 64 level-0 conv 1.53 -> 1.24 ms, profiles/r06_c2_wtile_ab.txt)
+WgradCfg x3_wgrad_cfg(const unet_ctx* c, const WgGeom& g) {
+    const int CA = g.CA, CB = g.CB;
+    const int64_t P = g.P;
+    auto fits = [&](const Tile* t) {
+        return t && (t->taps == 3 ? wx3_row3_ok(*t, g) : CA % t->bm == 0 && CB % t->bn == 0);
+    };
+    const Tile* t = wx3_desc((CA % 128 == 0 && CB % 128 == 0) ? WX3_128x128 : WX3_64x64);
+    if (fits(wx3_desc(WX3_R3_64x128))) t = wx3_desc(WX3_R3_64x128);
+    else if (fits(wx3_desc(WX3_R3_64x64))) t = wx3_desc(WX3_R3_64x64);
+    if (fits(wx3_desc(c->opt.x3_wtile))) t = wx3_desc(c->opt.x3_wtile);
+    WgradCfg w;
+    w.t = t;
+    const bool tap_row = t->taps == 3;
+    const int64_t tiles = tap_row ? (int64_t)(CA / t->bm) * 3 * (CB / t->bn)
+                                  : (int64_t)(gather_taps(g.amode) * CA / t->bm) * (gather_taps(g.bmode) * CB / t->bn);
     // blocks per 128x128 one-tap block of work: by area (one-tap), half that (tap-row)
-    const int area = std::max(1, 16384 / (w.bm * w.bn));
-    const int64_t target = (int64_t)c->opt.x3_wblocks *
-                           (w.tile <= 1 ? area : tap_row ? std::max(1, area / 2) : area);
+    const int area = std::max(1, 16384 / (t->bm * t->bn));
+    const int64_t target = (int64_t)c->opt.x3_wblocks * (tap_row ? std::max(1, area / 2) : area);
     int64_t splits = std::max<int64_t>(1, (target + tiles - 1) / tiles);
     int64_t pps = (P + splits - 1) / splits;
     pps = (pps + 255) / 256 * 256;
     const int ww = tap_row ? c->opt.x3_wwaves : c->opt.x3_wwaves1;
-    if (w.tile <= 4 && ww > 0) {
+    if (ww > 0) {
         // (r05) exactly `ww` full waves of block slots (CUs x blocks per CU): at most that many
         // blocks, pixel splits in 32-pixel steps.  The 256-pixel rounding above can land a few
         // blocks past a wave boundary (1024: 2049 blocks on 2048 slots, -4 %)
-        const int64_t slots = (int64_t)c->cus * (w.tile == 4 || w.tile == 1 ? 2 : 1) * ww;
+        const int64_t slots = (int64_t)c->cus * t->per_cu * ww;
         const int64_t s = std::max<int64_t>(1, slots / tiles);
         pps = (P + s - 1) / s;
         pps = (pps + 31) / 32 * 32;
@@ -777,32 +791,96 @@ void use_x3(const unet_ctx* c, const Plan& p, RowGemmArgs& g, const uint16_t* im
     g.tgm = c->opt.tile_group ? -1 : 0;
 }
 
-std::string x3wlabel(const char* fam, const WgradCfg& w, int layer) {
-    char b[112];
-    snprintf(b, sizeof b, "%s/wx3%s_%dx%d|%d", fam, w.tile >= 2 ? "r3" : "", w.bm, w.bn, layer);
+// launch labels, printed from the descriptor (tests/kernel_cases.py and profiles/kernel_coverage.txt
+// parse them): <site>/<kernel><tag>_<BM>x<BN>[x<BK> | s<stages>]|<layer> (rowgemm: the tag last)
+std::string tile_label(const char* site, const char* kernel, const char* tag, const Tile& t, const char* third,
+                       int layer, const char* tag_last = "") {
+    char b[112], k[16] = "";
+    if (third) snprintf(k, sizeof k, "%s%d", third, t.bk);
+    snprintf(b, sizeof b, "%s/%s%s_%dx%d%s%s|%d", site, kernel, tag, t.bm, t.bn, k, tag_last, layer);
     return b;
 }
 
-std::string xlabel(const char* fam, int tile, int layer) {
-    int bm = 0, bn = 0;
-    rowgemm_x3_tile_dims(tile, &bm, &bn);
-    char b[112];
-    snprintf(b, sizeof b, "%s/x3%s_%dx%d|%d", fam, tile >= 4 ? "r3" : "", bm, bn, layer);
-    return b;
+// Row-GEMM tile choice for an output width N (tiles.h ROW_TILES).
+//  * f32, N % 128 == 0: the software-pipelined 128x128 kernel, forward with its global loads
+//    two chunks ahead, dgrad too since r03 (one chunk ahead, removed in r06).  r02
+//    A/B (config 2):
+//    401 img/s against 390 for the register-staged tiles (t7 / t4 / t0 by grid size), the
+//    dominant kernel 128.9 vs 122.2 TF/s; the two schedules store identical bits
+//    (tests/test_gpu_parity.py::test_pipe_gemm_bit_identical);
+//  * f32, N = 64 outputs: the pipelined 128x64 with loads two chunks ahead on the
+//    forward GEMMs (level-0 128 -> 64 conv 112 -> 117 TF/s), the register-staged 128x64
+//    on the ConvT forward and since r03 the three-blocks-per-CU tiles on the dgrads
+//    (options tile_n64 / tile_n64_dgrad / tile_convt64; profiles/r02_pipe_exp.txt).
+// bf16 MFMA (register-staged): a chunk of 64 K per barrier (4 MFMA k-steps) by default.
+// Options tile_* override (tuning runs; -1 = automatic).
+int pick_tile(const unet_ctx* c, int N, bool dgrad, bool bf16, bool convt = false) {
+    const Options& o = c->opt;
+    if (bf16) return N % 128 == 0 ? RG_128x128K64 : RG_128x64;  // register-staged bf16 tiles
+    if (N % 64) return o.tile_n32;  // 32 outputs (narrow networks' level 0)
+    if (N % 128) return convt && !dgrad ? o.tile_convt64 : (dgrad ? o.tile_n64_dgrad : o.tile_n64);
+    if (convt && !dgrad && o.tile_convt >= 0) return o.tile_convt;
+    if (convt && dgrad && o.tile_convt_dgrad >= 0) return o.tile_convt_dgrad;
+    // dgrad on the two-chunks-ahead tile too since r03's prologue fence (loop waits vmcnt(2)
+    // -> vmcnt(8)): conv dgrads 23.4 -> 23.0 ms per step
+    if (dgrad) return o.tile_n128_dgrad >= 0 ? o.tile_n128_dgrad : RG_P128x128;
+    return o.tile_n128 >= 0 ? o.tile_n128 : RG_P128x128;
 }
 
-// tile and split-K partition of conv i's / ConvT k's weight gradient (p: N, H, W, P and rt set)
-WgradCfg conv_wgrad_cfg(const unet_ctx* c, const Plan& p, int i) {
-    const ConvL& L = c->conv[i];
-    const int Hl = p.H >> L.level, Wl = p.W >> L.level;
-    return p.rt.conv[i].wgrad == FAM_X3 ? x3_wgrad_cfg(c, L.cin, 9, L.cout, 1, p.P[L.level], Wl, Hl)
-                                        : wgrad_cfg(c, L.cin, 9, L.cout, 1, p.P[L.level], c->bf16, Wl);
+// the tile of one row GEMM of family fam (convt: a ConvT's forward or input gradient; its forward's
+// grid N is 4 cout and its f32 tile goes by cout)
+const Tile* row_pick(const unet_ctx* c, Family fam, const RowGeom& g, bool dgrad, bool convt) {
+    if (fam == FAM_X3) return &tile_or_none(x3_desc(x3_pick(c, g)));
+    if (fam == FAM_DMA16) return &tile_or_none(rg16_desc(rg16_pick(c, g)));
+    return &tile_or_none(row_desc(pick_tile(c, g.emode == E_CONVT ? g.cout : g.N, dgrad, c->bf16, convt)));
 }
-WgradCfg convt_wgrad_cfg(const unet_ctx* c, const Plan& p, int k) {
-    const ConvTL& T = c->convt[k];
-    return p.rt.convt[k].wgrad == FAM_X3 ? x3_wgrad_cfg(c, T.cin, 1, T.cout, 4, p.P[T.in_level])
-                                         : wgrad_cfg(c, T.cin, 1, T.cout, 4, p.P[T.in_level], c->bf16);
+
+// Tiles and splits, after the routes (p: N, H, W, P and rt.*.{fwd, dgrad, wgrad} set): every GEMM's
+// geometry -- the input gradients' epilogues follow from the block structure here, in one place --
+// its tile, and in a training plan the weight gradient's split-K partition.  make_plan sizes the
+// slabs from it; forward_impl, backward_impl, run_rowgemm and run_wgrad only read it.
+void plan_tiles(const unet_ctx* c, Plan& p, bool training) {
+    const int D = c->depth;
+    auto layer = [&](Route& q, int level, RowGeom f, RowGeom d, WgGeom wg, bool convt) {
+        f.M = d.M = (int)p.P[level];
+        f.W = d.W = wg.W = p.W >> level;
+        wg.H = p.H >> level;
+        wg.P = p.P[level];
+        if (q.fwd == FAM_NONE) return;
+        q.f = {f, row_pick(c, q.fwd, f, false, convt)};
+        if (!training) return;
+        q.d = {d, row_pick(c, q.dgrad, d, true, convt)};
+        q.w = q.wgrad == FAM_X3 ? x3_wgrad_cfg(c, wg) : wgrad_cfg(c, wg, c->bf16);
+        wg.pps = q.w.pps;
+        if (q.wgrad == FAM_DMA16) q.w.t16 = wg16_pick(c, wg);
+    };
+    for (int i = 0; i < c->nconv(); ++i) {
+        const ConvL& L = c->conv[i];
+        Route& q = p.rt.conv[i];
+        // the input gradient of a block's second conv is the `do` of the first one's BN (its
+        // epilogue emits that layer's partials); the residual block's first conv adds to the skip's
+        const int de = L.which == 1 ? E_STORE_BN : c->res ? E_ADD : E_STORE;
+        layer(q, L.level, {G_CONV3, c->bn_relu ? E_STATS : E_BIAS_RELU_STATS, 0, L.cout, 9 * L.cin, 0, 0},
+              {G_CONV3, de, 0, L.cin, 9 * L.cout, 0, 0}, {G_CONV3, G_IDENT, 0, L.cin, L.cout, 0, 0, 0}, false);
+        // option dz_in_wgrad: f32 register-staged weight-gradient tiles with the dz loader, with a
+        // dgrad to feed (every conv but the first)
+        q.dzw = training && q.wgrad == FAM_REG && !c->bf16 && c->opt.dz_in_wgrad && L.cin <= c->opt.dz_in_wgrad &&
+                q.dgrad == FAM_REG && i > 0 && q.w.t->dz;
+    }
+    for (int k = 0; k < D; ++k) {
+        const ConvTL& T = c->convt[k];
+        // (residual network: d(block output); the block's own backward entry masks it)
+        layer(p.rt.convt[k], T.in_level, {G_IDENT, E_CONVT, 0, 4 * T.cout, T.cin, 0, T.cout},
+              {G_UP2, c->res ? E_STORE : E_STORE_BN, 0, T.cin, 4 * T.cout, 0, 0},
+              {G_IDENT, G_UP2, 0, T.cin, T.cout, 0, 0, 0}, true);
+    }
+    for (int b = 1; b <= 2 * D && c->res; ++b) {
+        const ConvL& L = c->conv[2 * b];
+        layer(p.rt.skip[b], L.level, {G_IDENT, E_RESID, 0, L.cout, L.cin, 0, 0},
+              {G_IDENT, E_STORE, 0, L.cin, L.cout, 0, 0}, {G_IDENT, G_IDENT, 0, L.cin, L.cout, 0, 0, 0}, false);
+    }
 }
+
 
 void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan& p) {
     Bump b{base};
@@ -812,6 +890,7 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
     p.W = W;
     for (int l = 0; l <= D; ++l) p.P[l] = (int64_t)N * (H >> l) * (W >> l);
     p.rt = make_routes(c, training, p.P[0]);
+    plan_tiles(c, p, training);
     p.y.assign(NC, nullptr);
     p.ldy.assign(NC, 0);
     p.offy.assign(NC, 0);
@@ -939,18 +1018,17 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
         int64_t smax = 0, bmax = 0;
         for (int i = 1; i < NC; ++i) {
             const ConvL& L = c->conv[i];
-            const WgradCfg w = conv_wgrad_cfg(c, p, i);
+            const WgradCfg& w = p.rt.conv[i].w;
             smax = std::max(smax, (int64_t)w.splits * 9 * L.cin * L.cout);
             bmax = std::max(bmax, (int64_t)w.splits * L.cout);
         }
         for (int blk = 1; blk <= 2 * D && c->res; ++blk) {
             const ConvL& L = c->conv[2 * blk];
-            WgradCfg w = wgrad_cfg(c, L.cin, 1, L.cout, 1, p.P[L.level], c->bf16);
-            smax = std::max(smax, (int64_t)w.splits * L.cin * L.cout);
+            smax = std::max(smax, (int64_t)p.rt.skip[blk].w.splits * L.cin * L.cout);
         }
         for (size_t k = 0; k < c->convt.size(); ++k) {
             const ConvTL& T = c->convt[k];
-            const WgradCfg w = convt_wgrad_cfg(c, p, (int)k);
+            const WgradCfg& w = p.rt.convt[k].w;
             smax = std::max(smax, (int64_t)w.splits * T.cin * 4 * T.cout);
             bmax = std::max(bmax, (int64_t)w.splits * 4 * T.cout);
         }
@@ -971,50 +1049,6 @@ void make_plan(unet_ctx* c, int N, int H, int W, bool training, char* base, Plan
         for (int l = 0; l < D; ++l) p.dcat[l] = nullptr;
     }
     p.bytes = b.off + 256;
-}
-
-// Row-GEMM tile choice for an output width N (tile ids: kernels_gemm.hip ROWGEMM_TILES,
-// 18, 19, 25, 26 = kernels_gemm_pipe.hip).
-//  * f32, N % 128 == 0: the software-pipelined 128x128 kernel, forward with its global loads
-//    two chunks ahead (18), dgrad too since r03 (one chunk ahead, tile 16, removed in r06).  r02
-//    A/B (config 2):
-//    401 img/s against 390 for the register-staged tiles (t7 / t4 / t0 by grid size), the
-//    dominant kernel 128.9 vs 122.2 TF/s; the two schedules store identical bits
-//    (tests/test_gpu_parity.py::test_pipe_gemm_bit_identical);
-//  * f32, N = 64 outputs: the pipelined 128x64 with loads two chunks ahead (19) on the
-//    forward GEMMs (level-0 128 -> 64 conv 112 -> 117 TF/s), the register-staged 128x64
-//    (t1) on the ConvT forward and since r03 the three-blocks-per-CU 25 / 26 on the dgrads
-//    (options tile_n64 / tile_n64_dgrad / tile_convt64; profiles/r02_pipe_exp.txt).
-// bf16 MFMA (register-staged): a chunk of 64 K per barrier (4 MFMA k-steps) by default.
-// Options tile_* override (tuning runs; -1 = automatic).
-int pick_tile(const unet_ctx* c, int N, bool dgrad, bool bf16, bool convt = false) {
-    const Options& o = c->opt;
-    if (bf16) return N % 128 == 0 ? 6 : 1;  // register-staged bf16 tiles (kernels_gemm.hip)
-    if (N % 64) return o.tile_n32;  // 32 outputs (narrow networks' level 0)
-    if (N % 128) return convt && !dgrad ? o.tile_convt64 : (dgrad ? o.tile_n64_dgrad : o.tile_n64);
-    if (convt && !dgrad && o.tile_convt >= 0) return o.tile_convt;
-    if (convt && dgrad && o.tile_convt_dgrad >= 0) return o.tile_convt_dgrad;
-    // dgrad on the two-chunks-ahead tile too since r03's prologue fence (loop waits vmcnt(2)
-    // -> vmcnt(8)): conv dgrads 23.4 -> 23.0 ms per step
-    if (dgrad) return o.tile_n128_dgrad >= 0 ? o.tile_n128_dgrad : 18;
-    return o.tile_n128 >= 0 ? o.tile_n128 : 18;
-}
-
-std::string tlabel(const char* fam, int tile, int layer) {
-    int bm = 0, bn = 0, bk = 0;
-    rowgemm_tile_dims(tile, &bm, &bn, &bk);
-    char b[112];
-    const int db = rowgemm_tile_dbuf(tile);  // 1 = two LDS images, 2 = pipelined
-    snprintf(b, sizeof b, "%s/rowgemm_%dx%dx%d%s|%d", fam, bm, bn, bk,
-             db == 3 ? "g" : db == 2 ? "p" : (db ? "d" : ""), layer);
-    return b;
-}
-
-std::string wlabel(const char* fam, const WgradCfg& w, int layer) {
-    char b[112];
-    snprintf(b, sizeof b, "%s/wgrad%s_%dx%dx%d|%d", fam, w.tile >= 20 ? "3" : "", w.bm, w.bn, w.bkp,
-             layer);
-    return b;
 }
 
 #define RUN(label, flop, expr)                            \
@@ -1106,14 +1140,6 @@ void set_weights(const unet_ctx* c, RowGemmArgs& g, const float* img) {
         g.bt = img;
 }
 
-std::string tlabel16(const char* fam, int tile, int layer) {
-    int bm = 0, bn = 0, st = 0;
-    rowgemm16_tile_dims(tile, &bm, &bn, &st);
-    char b[112];
-    snprintf(b, sizeof b, "%s/rg16%s_%dx%ds%d|%d", fam, (tile == 19 || tile == 20) ? "r3" : "",
-             bm, bn, st, layer);
-    return b;
-}
 // point g's A operand at the prepared bf16 image `img` (lda = C channels)
 void use_a16(const unet_ctx* c, const Plan& p, RowGemmArgs& g, const uint16_t* img, int C) {
     g.a16 = img;
@@ -1204,7 +1230,7 @@ bool ranges_overlap(const float* a, int64_t na, const float* b, int64_t nb) {
 // ------------------------------------------------------------------------------------
 // Describing and launching a GEMM.  A site fills RowGemmArgs / WgradArgs as the f32 /
 // register-staged kernels read them and names the image where its family (Route) reads one;
-// run_rowgemm / run_wgrad switch the operands over, pick the tile and label and launch.
+// run_rowgemm / run_wgrad switch the operands over, build the label and launch the plan's tile.
 // ------------------------------------------------------------------------------------
 // what the launch helpers of one forward / backward pass share
 struct Pass {
@@ -1213,15 +1239,19 @@ struct Pass {
     Launcher L;
 };
 
-// a row GEMM over the pixels of `level`
-RowGemmArgs rowgemm_at(const Plan& p, int level, int N, int K) {
+// a row GEMM over the pixels of `level`, as the plan fixed it
+RowGemmArgs rowgemm_at(const Plan& p, int level, const RowGeom& q) {
     RowGemmArgs g{};
     g.zero16 = p.zero16;
     g.H = p.H >> level;
-    g.W = p.W >> level;
-    g.M = (int)p.P[level];
-    g.N = N;
-    g.K = K;
+    g.W = q.W;
+    g.M = q.M;
+    g.N = q.N;
+    g.K = q.K;
+    g.C = q.K / gather_taps(q.amode);
+    g.amode = q.amode;
+    g.emode = q.emode;
+    g.cout = q.cout;
     return g;
 }
 
@@ -1249,10 +1279,9 @@ void set_operand(Args& g, const Operand& a) {
     g.arelu = a.relu;
 }
 
-// dgrad epilogue: the result is the `do` of BN layer j, so the store also emits that layer's
-// partials (masked first by the ReLU after the BN in BN -> ReLU order)
+// E_STORE_BN dgrad epilogue: the result is the `do` of BN layer j, so the store also emits that
+// layer's partials (masked first by the ReLU after the BN in BN -> ReLU order)
 void bn_epilogue(const unet_ctx* c, const Plan& p, RowGemmArgs& g, int j) {
-    g.emode = E_STORE_BN;
     g.ey = p.y[j];
     g.ldey = p.ldy[j];
     g.offey = p.offy[j];
@@ -1304,55 +1333,41 @@ void use_images(const unet_ctx* c, const Plan& p, WgradArgs& w, Family fam, cons
     w.xcd = fam == FAM_X3 ? 1 : xcd16_on(c);
 }
 
-// One row GEMM of family `fam`.  g: the GEMM as the f32 / register-staged kernel reads it, and
-// in g.a16 the prepared image ([pixels][g.C]) the other two families read instead.  wimg: the
-// weight image in the pack region (f32, or bf16 in the same slot; the x3 copy of the region
-// holds its x3 image at 3x the offset), or the 1x1 skip parameter itself.
-int run_rowgemm(Pass& ps, const char* site, int layer, double flop, Family fam, bool dgrad,
+// One row GEMM of family `fam` on the plan's tile.  g: the GEMM as the f32 / register-staged kernel
+// reads it, and in g.a16 the prepared image ([pixels][g.C]) the other two families read instead.
+// wimg: the weight image in the pack region (f32, or bf16 in the same slot; the x3 copy of the
+// region holds its x3 image at 3x the offset), or the 1x1 skip parameter itself.
+int run_rowgemm(Pass& ps, const char* site, int layer, double flop, Family fam, const Tile& t,
                 const float* wimg, RowGemmArgs& g) {
     unet_ctx* c = ps.c;
     Launcher& L = ps.L;
     if (fam == FAM_X3) {
         use_x3(c, ps.p, g, g.a16, g.C, ps.p.pack3 + 3 * (wimg - ps.p.pack));
-        const int tile = x3_tile(c, g);
-        RUN(xlabel(site, tile, layer), flop, launch_rowgemm_x3(g, tile, L.s));
+        RUN(tile_label(site, "x3", t.tag, t, nullptr, layer), flop, launch_rowgemm_x3(g, t.id, L.s));
         return 0;
     }
     set_weights(c, g, wimg);
     if (fam == FAM_DMA16) {
         use_a16(c, ps.p, g, g.a16, g.C);
-        const int tile = rg16_tile(c, g);
-        RUN(tlabel16(site, tile, layer), flop, launch_rowgemm16(g, tile, L.s));
+        RUN(tile_label(site, "rg16", t.tag, t, "s", layer), flop, launch_rowgemm16(g, t.id, L.s));
         return 0;
     }
-    // pick_tile's ConvT rules.  Invariant: only the ConvT forward stores through E_CONVT (its
-    // grid N is 4 cout; the tile goes by cout) and only the ConvT input gradient gathers through
-    // G_UP2.  A new GEMM with either mode that is no ConvT needs its own flag here.
-    const bool convt = g.emode == E_CONVT || g.amode == G_UP2;
-    const int tile = pick_tile(c, g.emode == E_CONVT ? g.cout : g.N, dgrad, c->bf16, convt);
-    RUN(tlabel(site, tile, layer), flop, launch_rowgemm(g, tile, L.s));
+    RUN(tile_label(site, "rowgemm", "", t, "x", layer, t.tag), flop, launch_rowgemm(g, t.id, L.s));
     return 0;
 }
 
-// One weight gradient of family `fam`, split as wc says.  tile16: the LDS-DMA tile where the
-// site picks it (-1 = option wg16_tile).
+// One weight gradient of family `fam`, tiled and split as wc says.
 int run_wgrad(Pass& ps, const char* site, int layer, double flop, Family fam, const WgradCfg& wc,
-              const WgradArgs& w, int tile16 = -1) {
-    unet_ctx* c = ps.c;
+              const WgradArgs& w) {
     Launcher& L = ps.L;
     if (fam == FAM_X3) {
-        RUN(x3wlabel(site, wc, layer), flop, launch_wgrad_x3(w, wc.tile, L.s));
+        RUN(tile_label(site, "wx3", wc.t->tag, *wc.t, nullptr, layer), flop, launch_wgrad_x3(w, wc.t->id, L.s));
     } else if (fam == FAM_DMA16) {
-        const int t = tile16 >= 0 ? tile16 : wg16_tile(c, w.CA, w.CB);
-        int bm = 0, bn = 0, st = 0;
-        wgrad16g_tile_dims(t, &bm, &bn, &st);
-        char lb[112];
         // (the tap-row kernels are 3x3 only)
-        snprintf(lb, sizeof lb, "%s/wg16%s_%dx%ds%d|%d", site,
-                 w.amode != G_CONV3 ? "" : t == 4 ? "r3" : t == 7 ? "r3m" : "", bm, bn, st, layer);
-        RUN(lb, flop, launch_wgrad16(w, t, L.s));
+        RUN(tile_label(site, "wg16", w.amode == G_CONV3 ? wc.t16->tag : "", *wc.t16, "s", layer), flop,
+            launch_wgrad16(w, wc.t16->id, L.s));
     } else {
-        RUN(wlabel(site, wc, layer), flop, launch_wgrad(w, wc.tile, L.s));
+        RUN(tile_label(site, "wgrad", wc.t->tag, *wc.t, "x", layer), flop, launch_wgrad(w, wc.t->id, L.s));
     }
     return 0;
 }
@@ -1416,16 +1431,13 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
             return stats_finalize(c, L, p, i, R, M, training, prm, bn_run, bn_cnt);
         }
         const Operand a = conv_input(c, p, i);
-        RowGemmArgs g = rowgemm_at(p, C.level, C.cout, 9 * C.cin);
+        RowGemmArgs g = rowgemm_at(p, C.level, rt.f.g);
         set_operand(g, a);
-        g.C = C.cin;
-        g.amode = G_CONV3;
         g.out = p.y[i];
         g.ldo = p.ldy[i];
         g.ooff = p.offy[i];
         g.bias = bias_ptr(prm, C.b);
         g.stats = p.stats;
-        g.emode = c->bn_relu ? E_STATS : E_BIAS_RELU_STATS;
         if (rt.fwd != FAM_REG) {
             uint16_t* img = conv_image(c, p, i);
             if (rt.up == W_PREP) {  // the whole image (over a skip half the max-pool may have stored)
@@ -1436,7 +1448,7 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
             }  // (else the max-pool, or the ConvT and the max-pool, stored the whole image)
             g.a16 = img;
         }
-        if (int rc = run_rowgemm(ps, "conv_fwd", i, 2.0 * M * C.cout * 9 * C.cin, rt.fwd, false,
+        if (int rc = run_rowgemm(ps, "conv_fwd", i, 2.0 * M * C.cout * 9 * C.cin, rt.fwd, *rt.f.t,
                                  p.pack + C.pf, g))
             return rc;
         return stats_finalize(c, L, p, i, bn_groups(M), M, training, prm, bn_run, bn_cnt);
@@ -1446,16 +1458,12 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
         const Route& rt = p.rt.convt[k];
         const int lo = T.in_level - 1;
         const Operand a = convt_input(c, p, k);
-        RowGemmArgs g = rowgemm_at(p, T.in_level, 4 * T.cout, T.cin);
+        RowGemmArgs g = rowgemm_at(p, T.in_level, rt.f.g);
         set_operand(g, a);
-        g.C = T.cin;
-        g.amode = G_IDENT;
         g.out = p.cat[lo];
         g.ldo = 2 * c->ch(lo);
         g.ooff = c->up_off(lo);
         g.bias = prm + T.b;
-        g.cout = T.cout;
-        g.emode = E_CONVT;
         if (rt.fwd != FAM_REG) {
             const bool x3 = rt.fwd == FAM_X3;
             uint16_t* kept = x3 ? p.t3[k] : p.t16[k];
@@ -1468,7 +1476,7 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
             const int idec = 2 * (D + 1 + k);
             if (p.rt.conv[idec].up == W_CONVT) (x3 ? g.out3 : g.out16) = conv_image(c, p, idec);
         }
-        return run_rowgemm(ps, "convT_fwd", 100 + k, 2.0 * g.M * g.N * g.K, rt.fwd, false,
+        return run_rowgemm(ps, "convT_fwd", 100 + k, 2.0 * g.M * g.N * g.K, rt.fwd, *rt.f.t,
                            p.pack + T.pf, g);
     };
 
@@ -1484,14 +1492,11 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
                                               p.offout[b], s));
             return 0;
         }
-        RowGemmArgs g = rowgemm_at(p, CL.level, CL.cout, CL.cin);
+        RowGemmArgs g = rowgemm_at(p, CL.level, rt.f.g);
         set_operand(g, conv_input(c, p, 2 * b));
-        g.C = CL.cin;
-        g.amode = G_IDENT;
         g.out = p.out[b];
         g.ldo = p.ldout[b];
         g.ooff = p.offout[b];
-        g.emode = E_RESID;
         g.ey = p.y[i2];
         g.ldey = p.ldy[i2];
         g.offey = p.offy[i2];
@@ -1500,7 +1505,7 @@ int forward_impl(unet_ctx* c, const float* prm, float* bn_run, int64_t* bn_cnt, 
         // LDS-DMA: from the image conv1 read (rounded once, read twice)
         if (rt.fwd == FAM_DMA16) g.a16 = conv_image(c, p, 2 * b);
         // (f32: the torch layout [co][ci] of the parameter is already Bt[n][k])
-        return run_rowgemm(ps, "skip_fwd", b, 2.0 * M * CL.cout * CL.cin, rt.fwd, false,
+        return run_rowgemm(ps, "skip_fwd", b, 2.0 * M * CL.cout * CL.cin, rt.fwd, *rt.f.t,
                            c->bf16 ? p.pack + c->skip_pf[b] : prm + c->skip_w[b], g);
     };
 
@@ -1588,10 +1593,10 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
     // route says pool_fuse: the max-pool backward's inputs (the encoder loop fills it)
     DzPool pool_src;
     // conv i backward from do_i (dense [P][cout]).
-    // dgrad -> dx (ld ldx).  bn_next: dx is the `do` of BN layer i-1 (second conv of a
-    // block), so the epilogue also emits that layer's partials; *rows = their count.
-    auto conv_bwd = [&](int i, const float* dout, float* dx, int ldx, bool bn_next,
-                        int* rows, bool accumulate = false) -> int {
+    // dgrad -> dx (ld ldx), with the epilogue the plan gave it (rt.d.g.emode): where dx is the
+    // `do` of BN layer i-1 (second conv of a block) it also emits that layer's partials;
+    // *rows = their count.
+    auto conv_bwd = [&](int i, const float* dout, float* dx, int ldx, int* rows) -> int {
         const ConvL& C = c->conv[i];
         const Route& rt = p.rt.conv[i];
         const int Hl = H >> C.level, Wl = W >> C.level;
@@ -1604,7 +1609,7 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
                                    C.b >= 0 ? grads + C.b : nullptr, s));
             return 0;
         }
-        const WgradCfg wc = conv_wgrad_cfg(c, p, i);
+        const WgradCfg& wc = rt.w;
         WgradArgs w = wgrad_at(c, p, C.level, wc);
         w.CA = C.cin;
         w.amode = G_CONV3;
@@ -1612,7 +1617,6 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         w.bmode = G_IDENT;
         w.Mw = 9 * C.cin;
         w.Nw = C.cout;
-        int t16 = -1;
         // the dz pass (dz_pass.h).  Outputs by family: x3 -> the x3 image (and the conv bias's
         // column partials); LDS-DMA dgrad / wgrad -> the bf16 image, with the f32 dz in place
         // only while a register-staged kernel still consumes it; else f32 in place
@@ -1621,10 +1625,9 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         const bool dz16 = rg16 || wg16;
         const bool f32 = !x3 && (!wg16 || !(dx && rg16));
         // option dz_in_wgrad: the weight gradient's B' loader forms dz from do and y (the
-        // bn_dz pass disappears) and its first A'-tile blocks store it for the dgrad; f32
-        // register-staged weight-gradient tiles only, with a dgrad to feed (both BN orders;
-        // BN -> ReLU forms dz unmasked, do already carries the ReLU mask)
-        const bool dzw = !x3 && p.gdz && C.cin <= c->opt.dz_in_wgrad && !dz16 && dx && (wc.tile < 10 || wc.tile >= 20);
+        // bn_dz pass disappears) and its first A'-tile blocks store it for the dgrad (both BN
+        // orders; BN -> ReLU forms dz unmasked, do already carries the ReLU mask)
+        const bool dzw = rt.dzw;
         if (!dzw) {
             DzArgs z;
             z.y = p.y[i], z.ld = p.ldy[i], z.off = p.offy[i];
@@ -1671,20 +1674,9 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
             w.bdznomask = dz_mask ? 0 : 1;
             w.lddz = C.cout;
             w.bias_slab = C.b >= 0 ? p.bslab : nullptr;
-            if (wg16) {
-                use_images(c, p, w, FAM_DMA16, p.x16[i]);
-                // (the split count, sized for >= 2048 128x128 tiles, gives >= 512 256x256 ones)
-                t16 = wg16_tile(c, C.cin, C.cout);
-                // option wg16_r3: the tap-row kernel (three taps per block from one halo row)
-                const int r3 = c->opt.wg16_r3;
-                // (r06) tile 7 also at W = 32 / 16 (the 32^2 level and the 16^2 bottleneck)
-                const bool deep = r3 == 7 && (Wl == 32 || Wl == 16) && (Hl * Wl) % 64 == 0 && P % 64 == 0;
-                if ((r3 == 4 || r3 == 7) && (Wl % 64 == 0 || deep) && C.cin % 128 == 0 && C.cout % 128 == 0 &&
-                    wc.pps % 64 == 0)
-                    t16 = r3;
-            }
+            if (wg16) use_images(c, p, w, FAM_DMA16, p.x16[i]);
         }
-        if ((rc = run_wgrad(ps, "conv_wgrad", i, flop, rt.wgrad, wc, w, t16))) return rc;
+        if ((rc = run_wgrad(ps, "conv_wgrad", i, flop, rt.wgrad, wc, w))) return rc;
         RUN("wgrad_reduce", 0,
             k_slab_reduce(p.slab, wc.splits, w.Mw, w.Nw, 0, C.cin, C.cout, grads + C.w, s));
         if (rt.wgrad != FAM_X3 && C.b >= 0)
@@ -1692,21 +1684,18 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         if (!dx) return 0;
         // the input gradient: A = dz (f32: in place in dout, or the copy the weight gradient
         // stored; LDS-DMA / x3: its scratch image)
-        RowGemmArgs g = rowgemm_at(p, C.level, C.cin, 9 * C.cout);
+        RowGemmArgs g = rowgemm_at(p, C.level, rt.d.g);
         g.a = dzw ? p.gdz : dout;
         g.lda = C.cout;
-        g.C = C.cout;
-        g.amode = G_CONV3;
         g.ay = p.y[i];
         g.lday = p.ldy[i];
         g.offay = p.offy[i];
         g.a16 = scratch_image(p, rt.dgrad);
         g.out = dx;
         g.ldo = ldx;
-        g.emode = accumulate ? E_ADD : E_STORE;
-        if (bn_next) bn_epilogue(c, p, g, i - 1);
+        if (g.emode == E_STORE_BN) bn_epilogue(c, p, g, i - 1);
         if (rows) *rows = bn_groups(P);
-        return run_rowgemm(ps, "conv_dgrad", i, flop, rt.dgrad, true, p.pack + C.pd, g);
+        return run_rowgemm(ps, "conv_dgrad", i, flop, rt.dgrad, *rt.d.t, p.pack + C.pd, g);
     };
     // ConvT k backward: dOut = up half of dcat[lo]; dx = `do` of its input's BN (partials ->
     // rows)
@@ -1724,7 +1713,7 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         const bool wimg = rt.wgrad != FAM_REG;
         if (wimg && (rc = prep_image(L, rt.wgrad, up, 0, T.cout, p.P[lo], scratch_image(p, rt.wgrad), T.cout)))
             return rc;
-        const WgradCfg wc = convt_wgrad_cfg(c, p, k);
+        const WgradCfg& wc = rt.w;
         WgradArgs w = wgrad_at(c, p, T.in_level, wc);
         w.xcd = xcd_remap_wgrad(c);
         set_operand(w, convt_input(c, p, k));
@@ -1752,19 +1741,14 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         if (!wimg && rt.dgrad != FAM_REG &&
             (rc = prep_image(L, rt.dgrad, up, 0, T.cout, p.P[lo], scratch_image(p, rt.dgrad), T.cout)))
             return rc;
-        RowGemmArgs g = rowgemm_at(p, T.in_level, T.cin, 4 * T.cout);
+        RowGemmArgs g = rowgemm_at(p, T.in_level, rt.d.g);
         set_operand(g, up);
-        g.C = T.cout;
-        g.amode = G_UP2;
         g.a16 = scratch_image(p, rt.dgrad);
         g.out = dx;
         g.ldo = T.cin;
-        if (c->res)  // d(block output); the block's own backward entry masks it
-            g.emode = E_STORE;
-        else
-            bn_epilogue(c, p, g, src);
+        if (g.emode == E_STORE_BN) bn_epilogue(c, p, g, src);
         *rows = bn_groups(Pin);
-        return run_rowgemm(ps, "convT_dgrad", 100 + k, flop, rt.dgrad, true, p.pack + T.pd, g);
+        return run_rowgemm(ps, "convT_dgrad", 100 + k, flop, rt.dgrad, *rt.d.t, p.pack + T.pd, g);
     };
     // gradient bucket b is final once stage bucket_stage[b] is done: record its event (a
     // channel-padded network first compacts the bucket's tensors into the caller's arena,
@@ -1804,7 +1788,7 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
                     k_res_first_wgrad(p.x_nhwc, G0, (int)P, CL.cout, p.hpart, RED_G,
                                       grads + c->skip_w[b], s));
             } else {
-                const WgradCfg wc = wgrad_cfg(c, CL.cin, 1, CL.cout, 1, P, c->bf16);
+                const WgradCfg& wc = rt.w;
                 WgradArgs w = wgrad_at(c, p, CL.level, wc);
                 w.xcd = xcd_remap_wgrad(c);
                 set_operand(w, conv_input(c, p, i1));
@@ -1821,22 +1805,19 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
                 if ((rc = run_wgrad(ps, "skip_wgrad", b, flop, rt.wgrad, wc, w))) return rc;
                 RUN("wgrad_reduce", 0, k_slab_reduce(p.slab, wc.splits, w.Mw, w.Nw, 2, CL.cin, CL.cout,
                                                      grads + c->skip_w[b], s));
-                RowGemmArgs g = rowgemm_at(p, CL.level, CL.cin, CL.cout);
+                RowGemmArgs g = rowgemm_at(p, CL.level, rt.d.g);
                 g.a = G0;
                 g.lda = CL.cout;
-                g.C = CL.cout;
-                g.amode = G_IDENT;
                 g.a16 = p.s16;
                 g.out = dx;
                 g.ldo = ldx;
-                g.emode = E_STORE;
-                if ((rc = run_rowgemm(ps, "skip_dgrad", b, flop, rt.dgrad, true, p.pack + c->skip_pd[b], g)))
+                if ((rc = run_rowgemm(ps, "skip_dgrad", b, flop, rt.dgrad, *rt.d.t, p.pack + c->skip_pd[b], g)))
                     return rc;
             }
             if ((rc = bn_finalize(i2, RED_G))) return rc;
-            if ((rc = conv_bwd(i2, G0, G1, CL.cout, true, &R))) return rc;
+            if ((rc = conv_bwd(i2, G0, G1, CL.cout, &R))) return rc;
             if ((rc = bn_finalize(i1, R))) return rc;
-            return conv_bwd(i1, G1, dx, ldx, false, nullptr, dx != nullptr);
+            return conv_bwd(i1, G1, dx, ldx, nullptr);
         };
         RUN("head_bwd", 2.0 * p.P[0] * c->base * c->out_ch * 2,
             k_head_bwd(p.out[2 * D], c->base, nullptr, nullptr, 0, prm + c->head_w, c->out_ch,
@@ -1880,9 +1861,9 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
     RUN("head_grad", 0, k_sum_partials(p.hpart, wide_g(p.P[0]), c->out_ch * c->base + c->out_ch,
                                        grads + c->head_w, s));
     if ((rc = bn_finalize(last, wide_g(p.P[0])))) return rc;
-    if ((rc = conv_bwd(last, G0, G1, c->base, true, &R))) return rc;
+    if ((rc = conv_bwd(last, G0, G1, c->base, &R))) return rc;
     if ((rc = bn_finalize(last - 1, R))) return rc;
-    if ((rc = conv_bwd(last - 1, G1, p.dcat[0], 2 * c->base, false, nullptr))) return rc;
+    if ((rc = conv_bwd(last - 1, G1, p.dcat[0], 2 * c->base, nullptr))) return rc;
     if ((rc = stage_done(0))) return rc;
     // ---- ConvT k, then block D+k (the block whose output it up-samples) ----
     for (int k = D - 1; k >= 0; --k) {
@@ -1890,14 +1871,14 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         const int i1 = 2 * b + 1, i0 = 2 * b;
         if ((rc = convT_bwd(k, G0, &R))) return rc;
         if ((rc = bn_finalize(i1, R))) return rc;
-        if ((rc = conv_bwd(i1, G0, G1, c->conv[i1].cin, true, &R))) return rc;
+        if ((rc = conv_bwd(i1, G0, G1, c->conv[i1].cin, &R))) return rc;
         if ((rc = bn_finalize(i0, R))) return rc;
         if (b > D) {
             const int l = c->conv[i0].level;  // input is CAT_l
-            if ((rc = conv_bwd(i0, G1, p.dcat[l], 2 * c->ch(l), false, nullptr))) return rc;
+            if ((rc = conv_bwd(i0, G1, p.dcat[l], 2 * c->ch(l), nullptr))) return rc;
         } else {
             // bottleneck: its input is pool[D-1]; G0 <- d pool[D-1]
-            if ((rc = conv_bwd(i0, G1, G0, c->conv[i0].cin, false, nullptr))) return rc;
+            if ((rc = conv_bwd(i0, G1, G0, c->conv[i0].cin, nullptr))) return rc;
         }
         if ((rc = stage_done(D - k))) return rc;
     }
@@ -1928,15 +1909,15 @@ int backward_impl(unet_ctx* c, const float* prm, const float* dlogits, float* gr
         cur = nxt;
         nxt = cur == G0 ? G1 : G0;
         if ((rc = bn_finalize(i1, Gmp))) return rc;
-        if ((rc = conv_bwd(i1, cur, nxt, C, true, &R))) return rc;
+        if ((rc = conv_bwd(i1, cur, nxt, C, &R))) return rc;
         cur = nxt;
         nxt = cur == G0 ? G1 : G0;
         if ((rc = bn_finalize(i0, R))) return rc;
         if (b > 0) {
-            if ((rc = conv_bwd(i0, cur, nxt, c->conv[i0].cin, false, nullptr))) return rc;
+            if ((rc = conv_bwd(i0, cur, nxt, c->conv[i0].cin, nullptr))) return rc;
             cur = nxt;
         } else {
-            if ((rc = conv_bwd(0, cur, nullptr, 0, false, nullptr))) return rc;
+            if ((rc = conv_bwd(0, cur, nullptr, 0, nullptr))) return rc;
         }
         if ((rc = stage_done(2 * D - b))) return rc;
     }

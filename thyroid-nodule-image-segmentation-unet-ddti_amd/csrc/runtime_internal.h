@@ -65,48 +65,48 @@ struct Options {
     int wgrad_row3 = 1;        // f32 3x3 wgrad on the one-row-of-taps kernel: 0 never,
                                // 1 every eligible layer (default: r02 A/B, conv wgrad
                                // 27.1 -> 24.4 ms/step), 2 layers with a 64-channel operand
-    int wgrad_row3_tile = -1;  // its tile (>= 20), -1 = by channel counts
+    int wgrad_row3_tile = -1;  // its tile (a WG3_* id), -1 = by channel counts
     int wgrad_blocks = 2048;       // split-K target (blocks) of the one-tap f32 weight gradients
     int rg16_bn_k = 0;             // rg16: E_STORE_BN GEMMs with K below this take the 128x128 tile
                                    // (8192 until the one-barrier halo kernel, r04: 0 is 1-1.5 %
                                    // faster on config 4, profiles/r04_c4_barrier_ab.txt)
     int wgrad16_blocks = 1536;     // split-K target (blocks) of the bf16 weight gradients
                                    // (config 4 A/B: 1536 +1.4 % over 2048, 1024 -4.7 %)
-    int wgrad_row3_big = 21;       // row3 tile where Cin, Cout % 128 == 0 (-1 = 23)
-    int wgrad_row3_n32 = 1;        // row3 weight gradients for 32-channel operands too (tiles 24..26,
+    int wgrad_row3_big = WG3_128x64;  // row3 tile where Cin, Cout % 128 == 0 (-1 = WG3_128x128)
+    int wgrad_row3_n32 = 1;        // row3 weight gradients for 32-channel operands too (WG3_32x32 ..,
                                    // one / two waves: the split-K target counts four-wave blocks)
     int wgrad_row3_blocks = 1536;  // split-K target (blocks) of the row3 weight gradients
                                    // (r02 sweep 512..2048: 1536 best, 391 vs 386 img/s)
-    int wgrad_tile_w = 0;      // f32 wgrad tile, both channel counts multiples of 128
-    int wgrad_tile_n = 7;      // ... 64-channel layers (64x64, 3 waves/SIMD)
+    int wgrad_tile_w = WG_128x128;  // f32 wgrad tile, both channel counts multiples of 128
+    int wgrad_tile_n = WG_64x64;    // ... 64-channel layers (3 waves/SIMD)
     int tile_n128 = -1;        // f32 row-GEMM tile, N % 128 == 0 (-1 = pick_tile's default)
     int tile_n128_dgrad = -1;  // ... dgrad-type
-    int tile_n64 = 19;         // ... N = 64 outputs (forward-type)
-    int tile_n64_dgrad = 25;   // ... N = 64, dgrad-type (pipelined 128x64 at three blocks per
+    int tile_n64 = RG_P128x64;  // ... N = 64 outputs (forward-type)
+    int tile_n64_dgrad = RG_P3_128x64;  // ... N = 64, dgrad-type (pipelined 128x64 at three blocks per
                                // CU: level-0 dgrads 1.50-1.55 -> 1.40-1.45 ms, r03)
-    int tile_convt64 = 1;      // ConvT forward with 64 output channels (grid N = 256)
-    int tile_n32 = 15;         // f32 row GEMMs with 32 outputs: 15 = 256 x 32 with operands
+    int tile_convt64 = RG_128x64;  // ConvT forward with 64 output channels (grid N = 256)
+    int tile_n32 = RG_256x32G;  // f32 row GEMMs with 32 outputs: 256 x 32 with operands
                                // straight from global memory (r04, ResUNet(32, 4) 263 -> 282
-                               // img/s, (16, 4) 419 -> 478), 14 = the LDS-staged 256 x 32
+                               // img/s, (16, 4) 419 -> 478), or RG_256x32, the LDS-staged one
     int tile_convt = -1;       // ConvT forward, >= 128 output channels (-1 = tile_n128's)
-    int tile_convt_dgrad = 26; // ConvT input gradient (-1 = tile_n128_dgrad's; 26 = pipelined
+    int tile_convt_dgrad = RG_P3_128x64A;  // ConvT input gradient (-1 = tile_n128_dgrad's; pipelined
                                // 128x64 at three blocks per CU: the K = 4 Cout short-K GEMMs
                                // with their BN-partials epilogue, 1.33 -> 1.15 ms per step)
     int rg16 = 1;              // bf16 row GEMMs on the LDS-DMA kernel (0: register-staged)
-    int rg16_tile = -1;        // its tile (-1 = per GEMM, rg16_tile())
-    int rg16_n128 = 20;        // rg16 tile of the GEMMs whose N is not a multiple of 256 (the
+    int rg16_tile = -1;        // its tile (-1 = per GEMM, rg16_pick())
+    int rg16_n128 = R16_H512x128;  // rg16 tile of the GEMMs whose N is not a multiple of 256 (the
                                // 128-output layers; -1 = 128x128, 6 = 512x128, 20 = 512x128 tap-row
                                // halo for 3x3 convs, 6 elsewhere; r04 config 4: 122.7 -> 124.8
                                // img/s with 20, 121.9 with 6)
     int rg16_n128_bn = 0;      // ... also for the short-K E_STORE_BN GEMMs (else 128x128)
-    int rg16_r3 = 1;           // 256x256 3x3-conv GEMMs (W >= 16) on the tap-row halo kernel (tile 19;
+    int rg16_r3 = 1;           // 256x256 3x3-conv GEMMs (W >= 16) on the tap-row halo kernel (R16_H256x256;
                                // config 4: +0.9..1.2 % over three A/B pairs, r03)
     int wg16 = 1;              // bf16 3x3 wgrad on the LDS-DMA transposed-read kernel
-    int wg16_tile = 2;         // its tile (2 = 256x256)
+    int wg16_tile = W16_256x256;  // its tile
     int convt16 = 1;           // bf16 training: the ConvT forward stores the up half of the
                                // decoder's concat straight into that conv's bf16 operand image
                                // (no f32 up half; its prep pass converts the skip half only)
-    int wg16_r3 = 7;           // 3x3 layers with W % 64 == 0 on the tap-row bf16 weight gradient:
+    int wg16_r3 = W16_R3M;     // 3x3 layers with W % 64 == 0 on the tap-row bf16 weight gradient:
                                // 7 = 16x16x32 MFMAs with the re-read stagger (r06, config 4
                                // +1.3 % over 4, profiles/r06_c4_wg16_ab.txt; also at W = 32 / 16,
                                // +1.4 %, r06_c4_deep_wgrad_ab.txt), 4 = 32x32x16, four LDS stages
@@ -126,10 +126,10 @@ struct Options {
                                // of 64 on the bf16 matrix cores through exact three-way operand
                                // splits (kernels_gemm_x3.hip; fp64 error below the f32 MFMA
                                // kernels'); 0 = the f32 MFMA kernels everywhere
-    int x3_tile = -1;          // its row-GEMM tile (-1 = x3_tile())
+    int x3_tile = -1;          // its row-GEMM tile (-1 = x3_pick())
     int x3_wtile = -1;         // its weight-gradient tile (-1 = by channel counts)
     int x3_wblocks = 1536;     // split-K target (blocks) of its 128x128 weight gradients
-    int x3_n64 = 2;            // its row-GEMM tile for 64 outputs (2 = 128x64, 3 = 256x64)
+    int x3_n64 = X3_128x64;    // its row-GEMM tile for 64 outputs (or X3_256x64)
     int x3_r3 = 1;             // its 256x128 3x3 GEMMs on the tap-row halo kernel (tile 4)
     int x3_wwaves = 3;         // tap-row x3 weight gradients: split-K so the grid is this many full
                                // waves of block slots (0 = the x3_wblocks target; r05,

@@ -70,7 +70,7 @@ int main(int argc, char** argv) {
         float* xo = dalloc((size_t)M * sh.Cin, 9, 0.f);
         for (int r = 0; r < rounds; ++r) {
             for (int tile = 0; tile < NT; ++tile) {
-                if (tile == 6) continue;  // bf16-oriented BK64 tile
+                if (tile == RG_128x128K64) continue;  // bf16-oriented BK64 tile
                 for (int op = 0; op < 2; ++op) {
                     RowGemmArgs g{};
                     g.H = sh.H; g.W = sh.W; g.M = M;
@@ -132,10 +132,10 @@ int main(int argc, char** argv) {
         size_t slab_n = 0;
         for (int r = 0; r < rounds; ++r)
             for (int v = 0; v < NW; ++v) {
-                int bm, bn, bkp;
-                if (wgrad_tile_dims(wids[v], &bm, &bn, &bkp) != 0) continue;
-                if (sh.Cin % bm || sh.Cout % bn) continue;
-                const long tiles = (long)(9 * sh.Cin / (bm * wgrad_tile_taps(wids[v]))) * (sh.Cout / bn);
+                const Tile* wt = wg_desc(wids[v]);  // tiles.h WG_TILES
+                if (!wt || sh.Cin % wt->bm || sh.Cout % wt->bn) continue;
+                const int bkp = wt->bk;
+                const long tiles = (long)(9 * sh.Cin / (wt->bm * wt->taps)) * (sh.Cout / wt->bn);
                 long sp = (2048 + tiles - 1) / tiles;
                 if (sp > M / (8 * bkp)) sp = M / (8 * bkp);
                 if (sp < 1) sp = 1;
