@@ -41,6 +41,9 @@
  *   unet_morphometry / _host        (new)                  per-component size and shape integers of
  *                                                           a label plane: area, moments, box, bit
  *                                                           quads, squared maximum Feret diameter
+ *   unet_lesion_echo / _host        (new)                  per-component grey-value histograms of
+ *                                                           the lesion and of a ring around it, and
+ *                                                           pooled co-occurrence counts (GLCM)
  *   unet_tta_views / _host          (new)                  flip / rotation test-time augmentation:
  *                                                           the dihedral views of a batch, view-major
  *   unet_tta_merge / _host          (new)                  un-warp the per-view logits, average
@@ -427,6 +430,38 @@ int unet_morphometry(unet_ctx* ctx, const int32_t* labels, const int32_t* count,
 int unet_morphometry_host(const int32_t* labels, const int32_t* count, int N, int H, int W,
                           int64_t max_rows, int64_t* table);
 
+/* Lesion echogenicity and texture: the grey values under every connected component and in a band
+ * around it, as integer counts (csrc/echo.h; kernel in csrc/kernels_echo.hip).  gray uint8[N, H, W];
+ * labels int32[N, H, W] and count int32[N] as unet_components writes them (anything <= 0 background);
+ * levels G in {8, 16, 32}; ring w in 0..16.  table int32[N, max_rows, 512 + G G], the row of label l
+ * at index l - 1:
+ *     0..255  lesion histogram: column g counts the pixels with label l and grey value g
+ *   256..511  ring histogram: the owner of a background pixel is the smallest positive label in the
+ *             (2 w + 1) x (2 w + 1) window around it, clipped to the plane (chessboard distance <= w,
+ *             ties to the lower label); column 256 + g of the owner's row counts the pixel.  w = 0
+ *             leaves these columns zero.
+ *   512...    pooled co-occurrence counts at the level q(g) = (g G) >> 8: for every pixel p and offset
+ *             (dy, dx) in (0, 1), (1, 1), (1, 0), (1, -1) whose neighbour lies in the plane and carries
+ *             p's label l, entry [q(p)][q(neighbour)] of row l gains one (ordered pairs, counted once,
+ *             the four directions summed; the caller symmetrises).
+ * Every count is at most 4 H W <= 2^26.  Rows at or beyond count[n] are zero.  A label above
+ * min(count[n], max_rows) is dropped without a memory access; count[n] > max_rows tells the caller.
+ * The call clears the table itself (uninitialised memory may be handed in) and uses no scratch.  All
+ * integer and exact: the device, the host twin and a NumPy restatement agree bit for bit, whatever
+ * the launch geometry and the order of the atomics.  One block per 64 x 32 tile stages the labels
+ * with a halo of max(w, 1) in LDS, finds the ring owners by a separable minimum there, and counts
+ * into a label-keyed LDS table (option echo_agg = 1: wave-aggregated adds) flushed by global integer
+ * atomics; labels beyond its slots add straight to global memory.
+ * A null pointer, N, H, W or max_rows < 1, H * W >= 2^31, levels outside {8, 16, 32} or ring outside
+ * 0..16 is UNET_ERR_INVALID; H or W above 4096, or N * max_rows >= 2^31, is UNET_ERR_SHAPE.  gray,
+ * labels, count and table are device memory; all work is enqueued on `stream` with no host
+ * synchronisation.  unet_lesion_echo_host is the HOST twin (host pointers, the same echo.h rules). */
+int unet_lesion_echo(unet_ctx* ctx, const uint8_t* gray, const int32_t* labels, const int32_t* count,
+                     int N, int H, int W, int64_t max_rows, int levels, int ring, int32_t* table,
+                     unet_stream_t stream);
+int unet_lesion_echo_host(const uint8_t* gray, const int32_t* labels, const int32_t* count, int N, int H,
+                          int W, int64_t max_rows, int levels, int ring, int32_t* table);
+
 /* Flip / rotation test-time augmentation (csrc/tta.h; kernels in csrc/kernels_tta.hip).  View k in
  * 0..7 has bits h = k & 1, v = (k >> 1) & 1, t = (k >> 2) & 1:
  *   T_k(x): y = x;  if t: y = y.swapaxes(-1, -2);  if v: y = y[..., ::-1, :];  if h: y = y[..., ::-1]
@@ -673,7 +708,7 @@ int unet_overlay_u8_host(const uint8_t* gray, const uint8_t* pred, const uint8_t
  *   tile_n32 tile_convt64 tile_convt tile_convt_dgrad rg16 rg16_tile rg16_bn_k rg16_r3 rg16_n128
  *   rg16_n128_bn wg16 wg16_tile wg16_r3 convt16 wg16t xcd16 xcd_remap dz_in_wgrad x3 x3_tile
  *   x3_wtile x3_wblocks x3_n64 x3_r3 head_fuse pool_fuse x3_wwaves x3_wwaves1 tile_group
- *   cc_tile morph_lds
+ *   cc_tile morph_lds echo_agg
  * Set them between steps, not between a forward and its backward: the workspace plan and
  * which saved images exist depend on them (x3, convt16, the bf16 kernel choices, ...), so
  * unet_backward returns UNET_ERR_INVALID when any option differs from those of the training

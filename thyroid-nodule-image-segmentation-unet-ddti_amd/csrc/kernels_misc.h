@@ -227,6 +227,16 @@ int k_morph_extent(const int* labels, const int* count, int N, int H, int W, int
 int k_morph_feret(const int* count, int N, int H, int W, int64_t max_rows, const MorphScratch& sc, int64_t* table,
                   hipStream_t s);
 
+// Lesion echogenicity and texture (kernels_echo.hip; columns, rules and the host twin in echo.h): the
+// table int32 [N][max_rows][512 + G G] of grey planes and the label planes unet_components writes.
+// clear zeroes the whole table, count adds every block's histograms and co-occurrence counts to it.
+// No scratch.  The callers have checked the arguments.
+bool echo_grid_ok(int N, int H, int W, int64_t max_rows);
+int k_echo_clear(int N, int64_t max_rows, int G, int32_t* table, hipStream_t s);
+// agg 0: one LDS atomic per lane and count (the A/B of tools/echo_time.py)
+int k_echo_count(const uint8_t* gray, const int* labels, const int* count, int N, int H, int W, int64_t max_rows,
+                 int G, int w, int agg, int32_t* table, hipStream_t s);
+
 // Test-time augmentation (kernels_tta.hip; rules in tta.h): the views of x, view-major, and the
 // merge of the per-view logits.  The callers have checked the arguments (ops_abi.hip).
 int k_tta_views(const float* x, int N, int C, int H, int W, uint32_t views, float* out, hipStream_t s);

@@ -1,5 +1,5 @@
 // The stand-alone entry points of include/unet_hip.h: losses, distance transform, surface and
-// lesion metrics, the Lovasz hinge loss, connected components, lesion morphometry, test-time augmentation, the threshold sweep, the predict-mode
+// lesion metrics, the Lovasz hinge loss, connected components, lesion morphometry, lesion echogenicity, test-time augmentation, the threshold sweep, the predict-mode
 // export (resize back + overlay), resize and the training augmentations, each with its host twin where
 // it has one.  None of them reads the layer graph
 // or a workspace plan (runtime.hip): they use the context's device, error string, launch timer
@@ -10,6 +10,7 @@
 #include "aug.h"
 #include "cc.h"
 #include "curve.h"
+#include "echo.h"
 #include "edt.h"
 #include "export.h"
 #include "morph.h"
@@ -375,6 +376,32 @@ int unet_morphometry_host(const int32_t* labels, const int32_t* count, int N, in
     if (morph_args_invalid(labels, count, table, N, H, W, max_rows)) return UNET_ERR_INVALID;
     if (!morph_shape_ok(H, W)) return UNET_ERR_SHAPE;
     return catch_to_status([&] { morphometry_host(labels, count, N, H, W, max_rows, table); });
+}
+
+// ---- lesion echogenicity and texture (kernels_echo.hip, echo.h) ----
+int unet_lesion_echo(unet_ctx* c, const uint8_t* gray, const int32_t* labels, const int32_t* count, int N, int H,
+                     int W, int64_t max_rows, int levels, int ring, int32_t* table, unet_stream_t stream) {
+    ABI_TRY
+    if (!c) return UNET_ERR_INVALID;
+    if (const char* e = echo_args_invalid(gray, labels, count, table, N, H, W, max_rows, levels, ring))
+        return fail(c, UNET_ERR_INVALID, "lesion_echo: %s", e);
+    if (!echo_shape_ok(H, W)) return fail(c, UNET_ERR_SHAPE, "lesion_echo: H, W <= %d", MORPH_MAX_SIDE);
+    if (!echo_grid_ok(N, H, W, max_rows))
+        return fail(c, UNET_ERR_SHAPE, "lesion_echo: batch too large for one launch");
+    Launcher ln{c, (hipStream_t)stream};
+    const int agg = c->opt.echo_agg;
+    if (int r = ln.run("echo/clear", 0, [&] { return k_echo_clear(N, max_rows, levels, table, ln.s); })) return r;
+    return ln.run("echo/count", 0, [&] {
+        return k_echo_count(gray, labels, count, N, H, W, max_rows, levels, ring, agg, table, ln.s);
+    });
+    ABI_CATCH(c)
+}
+
+int unet_lesion_echo_host(const uint8_t* gray, const int32_t* labels, const int32_t* count, int N, int H, int W,
+                          int64_t max_rows, int levels, int ring, int32_t* table) {
+    if (echo_args_invalid(gray, labels, count, table, N, H, W, max_rows, levels, ring)) return UNET_ERR_INVALID;
+    if (!echo_shape_ok(H, W)) return UNET_ERR_SHAPE;
+    return catch_to_status([&] { echo_host(gray, labels, count, N, H, W, max_rows, levels, ring, table); });
 }
 
 // ---- test-time augmentation (kernels_tta.hip, tta.h) ----

@@ -89,6 +89,7 @@ const OptionDesc OPTION_TABLE[] = {
     {"tile_group", &Options::tile_group},
     {"cc_tile", &Options::cc_tile},
     {"morph_lds", &Options::morph_lds},
+    {"echo_agg", &Options::echo_agg},
 };
 
 // Parameter table in the reference's named_parameters() order, layer tables, packing

@@ -148,6 +148,9 @@ struct Options {
     int morph_lds = 1;         // lesion morphometry: the reduce pass aggregates per block in an LDS table
                                // (0 = every run straight to global atomics; same table either way,
                                // profiles/morph_time.txt)
+    int echo_agg = 0;          // lesion echogenicity: 1 = every LDS add is first aggregated over the wave
+                               // (0 = one LDS atomic per lane, which measured faster on every
+                               // input; same table either way, profiles/echo_time.txt)
 };
 
 // A device buffer one feature's entry points own through the context, grown on demand (grow):

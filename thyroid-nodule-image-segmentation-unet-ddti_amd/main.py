@@ -144,6 +144,16 @@ def get_parser(argv=None):
                         "measured on the GPU at --pp_connectivity")
     p.add_argument("--pixel_spacing", type=float, default=None, metavar="MM",
                    help="--lesion_table: millimetres per pixel; adds feret_max_mm and area_mm2")
+    p.add_argument("--lesion_echo", action="store_true",
+                   help="--lesion_table: also measure every component's grey values on the GPU (histogram, a ring "
+                        "of surrounding tissue, co-occurrence texture) and append the echo columns: mean, spread, "
+                        "quantiles, entropy, lesion-to-ring ratio and contrast, hypo- / iso- / hyperechoic class, "
+                        "GLCM contrast, homogeneity, energy, correlation, entropy")
+    p.add_argument("--echo_ring", type=int, default=None, metavar="W",
+                   help="--lesion_echo: width in pixels of the ring of surrounding tissue, 0..16 (0: no ring; "
+                        f"default {ECHO_RING_DEFAULT})")
+    p.add_argument("--echo_levels", type=int, default=None, choices=(8, 16, 32),
+                   help=f"--lesion_echo: grey levels of the co-occurrence matrix (default {ECHO_LEVELS_DEFAULT})")
     p.add_argument("--lesion_shape", action="store_true",
                    help="test: also report how the largest predicted lesion's size and shape agree with the "
                         "annotated one's (Feret diameter, area, centroid, taller-than-wide), measured on the GPU")
@@ -168,11 +178,18 @@ def get_parser(argv=None):
     e = lesion_args_error(args)
     if e:
         p.error(e)
+    if args.echo_ring is None:
+        args.echo_ring = ECHO_RING_DEFAULT
+    if args.echo_levels is None:
+        args.echo_levels = ECHO_LEVELS_DEFAULT
     if args.mode == "predict":
         e = predict_args_error(args, int(os.environ.get("WORLD_SIZE", "1")))
         if e:
             p.error(e)
     return args
+
+
+ECHO_RING_DEFAULT, ECHO_LEVELS_DEFAULT = 8, 16  # what --echo_ring / --echo_levels are when not given
 
 
 def lesion_args_error(args):
@@ -183,6 +200,12 @@ def lesion_args_error(args):
         return f"--pixel_spacing must be positive millimetres per pixel, got {args.pixel_spacing}"
     if args.pixel_spacing is not None and not args.lesion_table:
         return "--pixel_spacing scales the columns of --lesion_table; pass that too"
+    if args.lesion_echo and not args.lesion_table:
+        return "--lesion_echo adds columns to lesions.csv: it needs --mode predict --lesion_table"
+    if not args.lesion_echo and (args.echo_ring is not None or args.echo_levels is not None):
+        return "--echo_ring and --echo_levels tune --lesion_echo; pass that too"
+    if args.echo_ring is not None and not 0 <= args.echo_ring <= 16:
+        return f"--echo_ring must be in 0..16, got {args.echo_ring}"
     return None
 
 
@@ -249,9 +272,10 @@ def predict(args):
                      pp=dict(keep_largest=args.pp_largest, min_area=args.pp_min_area, fill_holes=args.pp_fill_holes,
                              connectivity=args.pp_connectivity),
                      width=args.contour_width, alpha=args.overlay_alpha, bins=args.curve_bins,
-                     lesion_table=args.lesion_table)
+                     lesion_table=args.lesion_table, lesion_echo=args.lesion_echo, echo_ring=args.echo_ring,
+                     echo_levels=args.echo_levels)
     lines = [",".join(CSV_HEADER)]
-    lesions = [",".join(lesion_csv_header(args.pixel_spacing))]
+    lesions = [",".join(lesion_csv_header(args.pixel_spacing, args.lesion_echo))]
     for start in range(0, len(names), args.batch_size):
         chunk = names[start:start + args.batch_size]
         planes = [decode_u8(Image.open(os.path.join(args.input_dir, n))) for n in chunk]

@@ -12,7 +12,8 @@ from ._lib import HipError, HipUnavailable, LIB_PATH, load  # noqa: F401
 from .data import GpuResizeToTensor  # noqa: F401
 from .functional import (LovaszHingeFunction, boundary_loss, connected_components, connected_components_host,  # noqa: F401
                          curve_edges, curve_hist, curve_hist_host, curve_stats, curve_stats_host,
-                         curve_summary, distance_maps, lesion_metrics, lesion_metrics_host,
+                         curve_summary, distance_maps, echo_descriptors, echo_table, echo_table_host,
+                         lesion_echo, lesion_echo_host, lesion_metrics, lesion_metrics_host,
                          lesion_morphometry, lesion_morphometry_host, lovasz_hinge,
                          lovasz_hinge_host, lovasz_hinge_parts, overlay,
                          morphometry_table, morphometry_table_host, overlay_host, postprocess_mask, postprocess_mask_host, resize_back, resize_back_host,

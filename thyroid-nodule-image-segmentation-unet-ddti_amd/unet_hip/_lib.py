@@ -124,6 +124,10 @@ SIGNATURES = {
                                        c_void_p]),
     "unet_morphometry": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p]),
     "unet_morphometry_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "unet_lesion_echo": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int,
+                                 c_void_p, c_void_p]),
+    "unet_lesion_echo_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int,
+                                      c_void_p]),
     "unet_tta_views": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_uint32, c_void_p,
                                c_void_p]),
     "unet_tta_views_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_uint32, c_void_p]),

@@ -566,14 +566,23 @@ def shape_summary(sums):
     return out
 
 
-def lesion_csv_lines(name, table, count, pixel_spacing=None, connectivity=1):
+def lesion_csv_lines(name, table, count, pixel_spacing=None, connectivity=1, echo=None):
     """The lines of lesions.csv (no newline) for one frame: one per component, the ``LESION_COLUMNS``
     in pixels (integers as such, real numbers with four decimals, the orientation in radians), then
-    with a spacing in millimetres per pixel the ``LESION_COLUMNS_MM``.  table: int64 (rows, 16), count:
-    the frame's component count (rows beyond the table were dropped and write no line)."""
+    with a spacing in millimetres per pixel the ``LESION_COLUMNS_MM``, then with ``echo`` (the frame's
+    ``echo_table`` rows, int32 (rows, 512 + G^2)) the ``LESION_COLUMNS_ECHO`` of ``echo_descriptors``:
+    the reals with four decimals (``nan`` where undefined), and, by this file's integers-as-such rule,
+    the five columns that are whole numbers by construction (echo_median, echo_p10, echo_p90: grey
+    values; ring_pixels: a count; echo_class: -1, 0 or 1) without a decimal point.
+    table: int64 (rows, 16), count: the frame's component count (rows beyond the table were dropped
+    and write no line)."""
     k = min(int(count), int(table.shape[0]))
     d = shape_descriptors(table[:k], 1.0, connectivity)
     rows = (table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table)[:k]
+    if echo is not None:
+        if int(echo.shape[0]) < k:
+            raise ValueError(f"echo has {int(echo.shape[0])} rows for {k} components")
+        e = echo_descriptors(echo[:k])
     lines = []
     for i in range(k):
         f = [str(name), str(i + 1), str(int(rows[i][0])), f"{d['centroid_x'][i]:.4f}", f"{d['centroid_y'][i]:.4f}"]
@@ -584,8 +593,198 @@ def lesion_csv_lines(name, table, count, pixel_spacing=None, connectivity=1):
         if pixel_spacing is not None:
             sp = float(pixel_spacing)
             f += [f"{d['feret_max'][i] * sp:.4f}", f"{int(rows[i][0]) * sp * sp:.4f}"]
+        if echo is not None:
+            for c in LESION_COLUMNS_ECHO:
+                v = e[_ECHO_CSV_SOURCE.get(c, c)][i]
+                whole = c in _ECHO_CSV_INTEGERS and v == v
+                f.append(str(int(v)) if whole else f"{v:.4f}")
         lines.append(",".join(f))
     return lines
+
+
+# ---------------------------------------------------------------- lesion echogenicity and texture
+ECHO_LEVELS = (8, 16, 32)
+ECHO_MAX_RING = 16
+LESION_COLUMNS_ECHO = ("echo_mean", "echo_std", "echo_median", "echo_p10", "echo_p90", "echo_entropy", "ring_pixels",
+                       "ring_mean", "ring_std", "echo_ratio", "echo_cnr", "echo_class", "glcm_contrast",
+                       "glcm_homogeneity", "glcm_energy", "glcm_correlation", "glcm_entropy")
+# the CSV column -> the key of echo_descriptors, where they differ; the columns written as integers
+_ECHO_CSV_SOURCE = {"echo_mean": "mean", "echo_std": "std", "echo_median": "median", "echo_p10": "p10",
+                    "echo_p90": "p90", "echo_entropy": "entropy"}
+_ECHO_CSV_INTEGERS = ("echo_median", "echo_p10", "echo_p90", "ring_pixels", "echo_class")
+
+
+def _echo_args(gray, labels, count, max_rows, levels, ring):
+    """``_morph_args`` of labels and count; gray as contiguous uint8 of the labels' shape on their
+    device; levels and ring as checked ints."""
+    labels, count, max_rows = _morph_args(labels, count, max_rows)
+    gray = gray.detach()
+    if gray.dim() == 2:
+        gray = gray[None]
+    if gray.dtype != torch.uint8 or gray.shape != labels.shape or gray.device != labels.device:
+        raise ValueError(f"gray must be uint8 {tuple(labels.shape)} on the labels' device, got {gray.dtype} "
+                         f"{tuple(gray.shape)} on {gray.device}")
+    if isinstance(levels, bool) or levels not in ECHO_LEVELS:
+        raise ValueError(f"levels must be one of {ECHO_LEVELS}, got {levels!r}")
+    if isinstance(ring, bool) or not isinstance(ring, int) or not 0 <= ring <= ECHO_MAX_RING:
+        raise ValueError(f"ring must be an int in 0..{ECHO_MAX_RING}, got {ring!r}")
+    return gray.contiguous(), labels, count, max_rows, int(levels), int(ring)
+
+
+def echo_table(gray, labels, count, max_rows=None, levels=16, ring=8):
+    """The grey-value counts of every component of the label planes ``connected_components`` returned,
+    on the device and the current stream: int32 (N, max_rows, 512 + levels^2), row l - 1 for label l.
+    gray: uint8 (N, H, W), the planes the labels were found on.  Columns 0..255 the histogram of the
+    component's pixels; 256..511 the histogram of the background pixels within chessboard distance
+    ``ring`` that it owns (the smallest label in reach owns a pixel; ring 0: all zero); from 512 the
+    levels x levels co-occurrence counts of the quantised levels (g levels) >> 8 over the ordered pairs
+    (p, p + (0, 1)), (1, 1), (1, 0), (1, -1) inside the component, the four directions summed.  Rows
+    beyond count[n] are zero and components beyond max_rows are dropped (count says so).  All integer
+    and exact.  max_rows=None reads ``count.max()`` (the only host synchronisation)."""
+    rt = _boundary_runtime(labels, "echo_table")
+    gray, labels, count, max_rows, levels, ring = _echo_args(gray, labels, count, max_rows, levels, ring)
+    return rt.lesion_echo(gray, labels, count, max_rows, levels, ring)
+
+
+def echo_table_host(gray, labels, count, max_rows=None, levels=16, ring=8):
+    """``echo_table`` of CPU tensors through the library's host twin."""
+    _cc_cpu(labels, "echo_table_host")
+    gray, labels, count, max_rows, levels, ring = _echo_args(gray, labels, count, max_rows, levels, ring)
+    N, H, W = labels.shape
+    table = torch.empty((N, max(max_rows, 0), 512 + levels * levels), dtype=torch.int32)
+    _cc_host_call("unet_lesion_echo_host", gray, labels, count, N, H, W, max_rows, levels, ring, table)
+    return table
+
+
+def lesion_echo(x, gray, connectivity=1, kind=None, max_rows=None, levels=16, ring=8):
+    """``connected_components`` of x, then ``echo_table`` of its labels over gray, on the device: a
+    dict of ``table`` int32 (N, max_rows, 512 + levels^2), ``count`` int32 (N,) and ``labels``."""
+    labels, count = connected_components(x, connectivity, kind)
+    return {"table": echo_table(gray, labels, count, max_rows, levels, ring), "count": count, "labels": labels}
+
+
+def lesion_echo_host(x, gray, connectivity=1, kind=None, max_rows=None, levels=16, ring=8):
+    """``lesion_echo`` of CPU tensors through the library's host twins."""
+    labels, count = connected_components_host(x, connectivity, kind)
+    return {"table": echo_table_host(gray, labels, count, max_rows, levels, ring), "count": count, "labels": labels}
+
+
+def _hist_quantile(cum, n, p):
+    """The smallest g with 100 cum[g] >= p n (NumPy's ``inverted_cdf``), cum the running integer sum."""
+    for g, c in enumerate(cum):
+        if 100 * c >= p * n:
+            return g
+    return len(cum) - 1
+
+
+def _hist_moments(h):
+    """n and the integers n^k m_k (k = 2, 3, 4) of the central moments m_k of an integer histogram,
+    with S1 = sum g h[g]: exact in Python ints."""
+    n = sum(h)
+    s1 = sum(g * c for g, c in enumerate(h))
+    s2 = sum(g * g * c for g, c in enumerate(h))
+    s3 = sum(g ** 3 * c for g, c in enumerate(h))
+    s4 = sum(g ** 4 * c for g, c in enumerate(h))
+    m2 = n * s2 - s1 * s1
+    m3 = n * n * s3 - 3 * n * s1 * s2 + 2 * s1 ** 3
+    m4 = n ** 3 * s4 - 4 * n * n * s1 * s3 + 6 * n * s1 * s1 * s2 - 3 * s1 ** 4
+    return n, s1, m2, m3, m4
+
+
+def echo_descriptors(table, levels=None):
+    """Echogenicity and texture descriptors of the rows of an ``echo_table``, in NumPy float64 on the
+    host from the integer rows alone (moments formed in Python ints before the one division).  table:
+    int32 (..., 512 + levels^2) (a tensor or an array; levels=None reads it off the width); every
+    returned array has the shape ``table.shape[:-1]``.  A row without pixels gives zeros; a quantity
+    without a defined value gives nan (skewness of constant grey, anything of an empty ring, a ratio
+    over 0, the co-occurrence descriptors without a pair).
+
+    From the lesion histogram: ``pixels``, ``mean``, ``std`` (population), ``skewness``, ``kurtosis``
+    (excess), ``min``, ``max``, ``median``, ``p10``, ``p90`` (quantile p: the smallest g whose cumulative
+    count c has 100 c >= p n, NumPy's ``inverted_cdf``), ``entropy`` (bits over the 256 bins).  From the
+    ring histogram: ``ring_pixels``, ``ring_mean``, ``ring_std``, ``ring_p25``, ``ring_p75``.  Lesion
+    against ring: ``echo_ratio`` = mean / ring_mean, ``echo_cnr`` = |mean - ring_mean| / sqrt(std^2 +
+    ring_std^2), ``echo_class`` = -1 (hypoechoic) if median < ring_p25, +1 (hyperechoic) if median >
+    ring_p75, else 0 (isoechoic, and with an empty ring).  From P = (C + C^T) / (2 pairs) of the
+    co-occurrence counts C: ``glcm_pairs``, ``glcm_contrast`` = sum (i - j)^2 P, ``glcm_dissimilarity``
+    = sum |i - j| P, ``glcm_homogeneity`` = sum P / (1 + (i - j)^2), ``glcm_energy`` = sqrt(sum P^2),
+    ``glcm_correlation`` (1 when the level variance is 0), ``glcm_entropy`` (bits)."""
+    import math
+
+    import numpy as np
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    width = t.shape[-1] if t.ndim else 0
+    G = math.isqrt(max(width - 512, 0)) if levels is None else levels
+    if G not in ECHO_LEVELS or width != 512 + G * G or t.dtype != np.int32:
+        raise ValueError(f"table must be int32 (..., 512 + levels^2) with levels in {ECHO_LEVELS}, got {t.dtype} "
+                         f"{t.shape} (levels {levels!r})")
+    shape = t.shape[:-1]
+    rows = t.reshape(-1, width)
+    reals = ("mean", "std", "skewness", "kurtosis", "min", "max", "median", "p10", "p90", "entropy", "ring_mean",
+             "ring_std", "ring_p25", "ring_p75", "echo_ratio", "echo_cnr", "glcm_contrast", "glcm_dissimilarity",
+             "glcm_homogeneity", "glcm_energy", "glcm_correlation", "glcm_entropy")
+    out = {k: np.zeros(len(rows), np.float64) for k in reals}
+    for k in ("pixels", "ring_pixels", "glcm_pairs", "echo_class"):
+        out[k] = np.zeros(len(rows), np.int64)
+    nan = float("nan")
+    ii, jj = np.mgrid[:G, :G]
+    d2 = ((ii - jj) ** 2).astype(np.int64)
+
+    def entropy(counts, total):
+        p = counts[counts > 0].astype(np.float64) / total
+        return float(-(p * np.log2(p)).sum()) + 0.0  # one bin: 0, not -0
+
+    for r, row in enumerate(rows):
+        h = row[:256].tolist()
+        n, s1, m2, m3, m4 = _hist_moments(h)
+        if n <= 0:
+            continue
+        cum = np.cumsum(row[:256].astype(np.int64)).tolist()
+        mean, var = s1 / n, m2 / (n * n)
+        out["pixels"][r] = n
+        out["mean"][r], out["std"][r] = mean, math.sqrt(var)
+        out["skewness"][r] = m3 / math.sqrt(m2) ** 3 if m2 > 0 else nan
+        out["kurtosis"][r] = m4 / (m2 * m2) - 3 if m2 > 0 else nan
+        nz = [g for g, c in enumerate(h) if c]
+        out["min"][r], out["max"][r] = nz[0], nz[-1]
+        med = _hist_quantile(cum, n, 50)
+        out["median"][r], out["p10"][r], out["p90"][r] = med, _hist_quantile(cum, n, 10), _hist_quantile(cum, n, 90)
+        out["entropy"][r] = entropy(row[:256], n)
+        # the ring
+        rn, rs1, rm2, _, _ = _hist_moments(row[256:512].tolist())
+        out["ring_pixels"][r] = rn
+        if rn > 0:
+            rcum = np.cumsum(row[256:512].astype(np.int64)).tolist()
+            rmean, rvar = rs1 / rn, rm2 / (rn * rn)
+            p25, p75 = _hist_quantile(rcum, rn, 25), _hist_quantile(rcum, rn, 75)
+            out["ring_mean"][r], out["ring_std"][r] = rmean, math.sqrt(rvar)
+            out["ring_p25"][r], out["ring_p75"][r] = p25, p75
+            out["echo_ratio"][r] = mean / rmean if rs1 > 0 else nan
+            out["echo_cnr"][r] = abs(mean - rmean) / math.sqrt(var + rvar) if m2 > 0 or rm2 > 0 else nan
+            out["echo_class"][r] = -1 if med < p25 else (1 if med > p75 else 0)
+        else:
+            for k in ("ring_mean", "ring_std", "ring_p25", "ring_p75", "echo_ratio", "echo_cnr"):
+                out[k][r] = nan
+        # the co-occurrence matrix
+        C = row[512:].astype(np.int64).reshape(G, G)
+        S = C + C.T  # 2 pairs P
+        T = int(S.sum())
+        out["glcm_pairs"][r] = T // 2
+        if T == 0:
+            for k in reals:
+                if k.startswith("glcm_"):
+                    out[k][r] = nan
+            continue
+        out["glcm_contrast"][r] = int((d2 * S).sum()) / T
+        out["glcm_dissimilarity"][r] = int((np.abs(ii - jj) * S).sum()) / T
+        out["glcm_homogeneity"][r] = float((S / (1.0 + d2)).sum()) / T
+        out["glcm_energy"][r] = math.sqrt(int((S * S).sum())) / T
+        marg = S.sum(axis=1)
+        a, b = int((np.arange(G) * marg).sum()), int((np.arange(G) ** 2 * marg).sum())
+        cij = int((ii * jj * S).sum())
+        out["glcm_correlation"][r] = (T * cij - a * a) / (T * b - a * a) if T * b - a * a > 0 else 1.0
+        out["glcm_entropy"][r] = entropy(S, T)
+    return {k: v.reshape(shape) for k, v in out.items()}
 
 
 # ---------------------------------------------------------------- test-time augmentation

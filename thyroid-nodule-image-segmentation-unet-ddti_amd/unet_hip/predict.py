@@ -12,7 +12,10 @@ the optional ``postprocess_mask`` there, ``overlay`` on the frame itself and a c
 count.  Nothing comes back to the host but one row of seven integers per frame, in one transfer.
 With ``lesion_table=True`` the labels of that count are kept, the frames of one size share one
 ``morphometry_table`` call, and the sixteen integers of every component come back in a second transfer
-(``out["lesions"]``, the rows of lesions.csv).
+(``out["lesions"]``, the rows of lesions.csv).  With ``lesion_echo=True`` too, the same groups go with
+the frames' own grey planes through one ``echo_table`` call each, and the histograms and co-occurrence
+counts of every component come back in one more transfer (``out["echo"]``, the echo columns of
+lesions.csv).
 """
 import numpy as np
 import torch
@@ -54,7 +57,7 @@ def check_predict_options(tta, threshold):
 
 class Predictor:
     def __init__(self, model, image_size, device, tta="none", tta_merge="prob", threshold=0.5, pp=None, width=1,
-                 alpha=0, bins=256, lesion_table=False):
+                 alpha=0, bins=256, lesion_table=False, lesion_echo=False, echo_ring=8, echo_levels=16):
         self.device = torch.device(device)
         self.model = model.to(self.device).eval()
         self.pipe = GpuResizeToTensor(image_size, self.device)
@@ -79,6 +82,14 @@ class Predictor:
         self.post = self.pp["keep_largest"] or self.pp["min_area"] > 0 or self.pp["fill_holes"]
         self.width, self.alpha = int(width), int(alpha)
         self.lesion_table = bool(lesion_table)
+        self.lesion_echo = bool(lesion_echo)
+        if self.lesion_echo and not self.lesion_table:
+            raise ValueError("lesion_echo=True adds columns to the lesion table; pass lesion_table=True too")
+        if echo_levels not in F.ECHO_LEVELS:
+            raise ValueError(f"echo_levels must be one of {F.ECHO_LEVELS}, got {echo_levels!r}")
+        if not isinstance(echo_ring, int) or isinstance(echo_ring, bool) or not 0 <= echo_ring <= F.ECHO_MAX_RING:
+            raise ValueError(f"echo_ring must be an int in 0..{F.ECHO_MAX_RING}, got {echo_ring!r}")
+        self.echo_ring, self.echo_levels = int(echo_ring), int(echo_levels)
 
     def _forward(self, gray, planes):
         """(N, S, S) float32: the score planes at the network resolution of the uploaded frames
@@ -90,24 +101,36 @@ class Predictor:
             return F.tta_predict(self.model, x, self.tta, self.tta_merge)["score"][:, 0].contiguous()
         return self.model(x).detach().float()[:, 0].contiguous()
 
-    def _lesions(self, labels, counts):
+    def _lesions(self, labels, counts, grays=None):
         """Per frame the int64 (count, 16) table rows on the host: the frames of one size are one
-        ``morphometry_table`` call (max_rows their largest count), all tables one transfer."""
+        ``morphometry_table`` call (max_rows their largest count), all tables one transfer.  With the
+        frames' grey planes ``grays``, a second list too: per frame the int32 (count, 512 + G^2)
+        ``echo_table`` rows, the same groups one call each and all of them one more transfer."""
         groups = {}
         for i, (lab, _) in enumerate(labels):
             if counts[i] > 0:
                 groups.setdefault(tuple(lab.shape[1:]), []).append(i)
-        flat, where = [], {}
+        width = 512 + self.echo_levels ** 2
+        flat, flat_e, where = [], [], {}
         for idx in groups.values():
             rows = max(counts[i] for i in idx)
-            tab = F.morphometry_table(torch.cat([labels[i][0] for i in idx]), torch.cat([labels[i][1] for i in idx]),
-                                      rows)
+            lab, cnt = torch.cat([labels[i][0] for i in idx]), torch.cat([labels[i][1] for i in idx])
+            tab = F.morphometry_table(lab, cnt, rows)
+            if grays is not None:
+                etab = F.echo_table(torch.stack([grays[i] for i in idx]), lab, cnt, rows, self.echo_levels,
+                                    self.echo_ring)
             for j, i in enumerate(idx):
                 where[i] = (sum(t.shape[0] for t in flat), counts[i])
                 flat.append(tab[j, :counts[i]])
+                if grays is not None:
+                    flat_e.append(etab[j, :counts[i]])
         back = torch.cat(flat).cpu() if flat else torch.zeros((0, 16), dtype=torch.int64)  # the one transfer
         empty = torch.zeros((0, 16), dtype=torch.int64)
-        return [back[where[i][0]:where[i][0] + where[i][1]] if i in where else empty for i in range(len(labels))]
+        cut = lambda t, e: [t[where[i][0]:where[i][0] + where[i][1]] if i in where else e for i in range(len(labels))]
+        if grays is None:
+            return cut(back, empty)
+        back_e = torch.cat(flat_e).cpu() if flat_e else torch.zeros((0, width), dtype=torch.int32)  # one more
+        return cut(back, empty), cut(back_e, torch.zeros((0, width), dtype=torch.int32))
 
     @torch.no_grad()
     def scores(self, planes):
@@ -121,7 +144,9 @@ class Predictor:
         ``scores`` (float32 (h, w), when asked), all on the device, and ``rows`` (dicts of Python ints:
         h, w, area, contour, x0, y0, x1, y1, components).  Every frame is uploaded once.  With
         ``lesion_table``, ``lesions`` too: per frame the int64 (components, 16) rows of
-        ``morphometry_table`` on the host."""
+        ``morphometry_table`` on the host, and with ``lesion_echo`` ``echo``: per frame the int32
+        (components, 512 + echo_levels^2) rows of ``echo_table`` of the frame's own grey plane and the
+        labels of its final mask, on the host."""
         grays = [self.pipe.upload(im) for im in planes]
         score = self._forward(grays, planes)
         masks, overlays, planes_out, stats, labels = [], [], [], [], []
@@ -146,7 +171,9 @@ class Predictor:
             row.update(zip(ROW_FIELDS, (int(v) for v in r)))
             rows.append(row)
         out = dict(masks=masks, overlays=overlays, rows=rows)
-        if self.lesion_table:
+        if self.lesion_echo:
+            out["lesions"], out["echo"] = self._lesions(labels, [r["components"] for r in rows], grays)
+        elif self.lesion_table:
             out["lesions"] = self._lesions(labels, [r["components"] for r in rows])
         if return_scores:
             out["scores"] = planes_out
@@ -155,16 +182,19 @@ class Predictor:
 
 def lesion_lines(out, names, pixel_spacing=None, connectivity=1):
     """The lines of lesions.csv (no header) for what a ``Predictor`` with ``lesion_table`` returned for
-    the frames ``names``: one per component, none for an empty mask (``F.lesion_csv_lines``)."""
+    the frames ``names``: one per component, none for an empty mask (``F.lesion_csv_lines``); with the
+    echo columns when the ``Predictor`` had ``lesion_echo``."""
     import os
     lines = []
-    for name, tab in zip(names, out["lesions"]):
-        lines += F.lesion_csv_lines(os.path.basename(name), tab, tab.shape[0], pixel_spacing, connectivity)
+    echo = out.get("echo") or [None] * len(names)
+    for name, tab, e in zip(names, out["lesions"], echo):
+        lines += F.lesion_csv_lines(os.path.basename(name), tab, tab.shape[0], pixel_spacing, connectivity, e)
     return lines
 
 
-def lesion_csv_header(pixel_spacing=None):
-    return F.LESION_COLUMNS + (F.LESION_COLUMNS_MM if pixel_spacing is not None else ())
+def lesion_csv_header(pixel_spacing=None, echo=False):
+    return (F.LESION_COLUMNS + (F.LESION_COLUMNS_MM if pixel_spacing is not None else ())
+            + (F.LESION_COLUMNS_ECHO if echo else ()))
 
 
 def save_predictions(out, names, output_dir, save_scores=False):

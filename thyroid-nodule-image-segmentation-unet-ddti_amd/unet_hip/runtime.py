@@ -287,6 +287,16 @@ class UNetRuntime:
         _lib.check(rc, self.ctx, "unet_morphometry")
         return table
 
+    def lesion_echo(self, gray, labels, count, max_rows, levels, ring):
+        """table int32 (N, max_rows, 512 + levels^2) of gray uint8 (N, H, W), labels int32 (N, H, W) and
+        count int32 (N,) (unet_lesion_echo; the columns in csrc/echo.h).  The call clears the table."""
+        N, H, W = labels.shape
+        table = torch.empty((N, max_rows, 512 + levels * levels), dtype=torch.int32, device=labels.device)
+        rc = self.lib.unet_lesion_echo(self.ctx, _lib.ptr(gray), _lib.ptr(labels), _lib.ptr(count), N, H, W,
+                                       max_rows, levels, ring, _lib.ptr(table), _lib.stream_ptr(labels.device))
+        _lib.check(rc, self.ctx, "unet_lesion_echo")
+        return table
+
     def tta_views(self, x, views):
         """(K N, C, H, W): the views of x (N, C, H, W) in ascending k, view-major (unet_tta_views;
         views is the bit mask)."""
