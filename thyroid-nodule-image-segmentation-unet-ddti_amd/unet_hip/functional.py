@@ -822,6 +822,9 @@ def _tta_mode(mode):
     return TTA_MODES[mode]
 
 
+tta_mode = _tta_mode  # the public name: the code of a merge mode, or the refusal of an unknown one
+
+
 def _tta_4d(x, what):
     if x.dim() != 4:
         raise ValueError(f"{what} must be (N, C, H, W), got {tuple(x.shape)}")

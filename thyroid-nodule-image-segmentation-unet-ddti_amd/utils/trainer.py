@@ -69,7 +69,9 @@ from torch.optim.lr_scheduler import CosineAnnealingWarmRestarts
 import unet_hip
 from models.loss import BoundaryLoss, LovaszHingeLoss
 from unet_hip.dist import DistributedUNet
-from utils.utils import AverageMeter, EarlyStopping, global_metrics_from_counts, metrics_from_counts
+from utils import test_blocks as TB
+from utils.test_blocks import all_reduce, distributed as _distributed
+from utils.utils import AverageMeter, EarlyStopping, metrics_from_counts
 
 try:
     from torch.utils.tensorboard import SummaryWriter
@@ -97,10 +99,6 @@ try:
 except Exception:
     def tqdm(it, **k):
         return it
-
-
-def _distributed():
-    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
 
 
 def _is_rank0():
@@ -218,11 +216,6 @@ class Trainer:
         n = max(float(v[-1]), 1.0)
         return v[:-1] / n, n
 
-    def _reduce_counts(self, c):
-        if _distributed():
-            dist.all_reduce(c)
-        return c
-
     def _log_epoch(self, tag, epoch, meters, counts):
         acc, precision, recall, f1, iou = metrics_from_counts(counts.tolist())
         bce, dice, focal, bnd, tot = (m.avg for m in meters[:5])
@@ -309,7 +302,7 @@ class Trainer:
         totals, n_glob = self._reduce_scalars(sums, n_seen)
         for m, v in zip(meters, totals.tolist()):
             m.update(v, n_glob)  # the global count: identical meters on every rank
-        return meters, self._reduce_counts(counts)
+        return meters, all_reduce(counts)
 
     # -------------------------------------------------------------- reference API
     def train_one_epoch(self, epoch):
@@ -355,226 +348,49 @@ class Trainer:
         accumulated on the device.  The contour-overlay PNGs (:262-299) are written only when
         matplotlib and scikit-image are importable; ``save_overlays`` (default
         ``config.save_overlays``) writes one device-rendered ``test_overlay_<index>.png`` per sample
-        whether they are or not."""
+        whether they are or not.  Every block of the report is a class of ``utils/test_blocks.py``: this is
+        the loop that feeds them each batch and then reports what each one found, in the list's order."""
         if save_overlays is None:
             save_overlays = bool(getattr(self.config, "save_overlays", False))
         self.logger.info("------------------Starting Testing Model------------------")
         self.model.eval()
         if self.ddp is not None:  # every shard evaluated with replica 0's BN buffers (DataParallel)
             self.ddp.sync_buffers()
-        counts = torch.zeros(6, dtype=torch.int64, device=self.device)
+        sw = TB.Switches(self.config, self.device, self.rt)
+        if sw.criterion is not None:  # the validation split decides the operating point
+            val = tqdm(self.val_loader, desc="Threshold sweep (val)", leave=True)
+            vs = TB.Curve(sw).sweep(self.model, val).summary()
+            sw.opt_k = vs["best_global_k" if sw.criterion == "val-dice" else "best_image_k"]
+        blocks = [TB.Plain(sw),
+                  sw.tta_on and TB.TTA(sw),
+                  sw.surface and TB.Surface(sw),
+                  sw.post and TB.PostProcessed(sw),
+                  sw.lesion and TB.Lesion(sw),
+                  sw.curve and TB.Curve(sw),
+                  sw.opt and TB.OperatingPoint(sw),
+                  sw.shape and TB.Shape(sw)]
+        blocks = [b for b in blocks if b]
         total = 0
         keep = []
-        surface = bool(getattr(self.config, "surface_metrics", False))
-        if surface:  # sums of hd95, hd, assd over the defined samples; defined, undefined
-            ssums = torch.zeros(5, dtype=torch.float64, device=self.device)
-        cfg = self.config
-        pp = dict(keep_largest=bool(getattr(cfg, "pp_largest", False)),
-                  min_area=int(getattr(cfg, "pp_min_area", 0) or 0),
-                  fill_holes=bool(getattr(cfg, "pp_fill_holes", False)),
-                  connectivity=int(getattr(cfg, "pp_connectivity", 1) or 1))
-        post = pp["keep_largest"] or pp["min_area"] > 0 or pp["fill_holes"]
-        lesion = bool(getattr(cfg, "lesion_metrics", False))
-        shape = bool(getattr(cfg, "lesion_shape", False))
-        shape_rows = []  # per batch: the table rows of the largest predicted and annotated component
-        if post:  # the same sums for the post-processed masks
-            pcounts = torch.zeros(6, dtype=torch.int64, device=self.device)
-            psums = torch.zeros(5, dtype=torch.float64, device=self.device)
-        if lesion:  # n_pred, n_gt, gt_hit, pred_hit over the test set
-            lsums = torch.zeros(4, dtype=torch.int64, device=self.device)
-        tta = str(getattr(cfg, "tta", None) or "none")
-        tta_mode = str(getattr(cfg, "tta_merge", None) or "prob")
-        tta_on = tta != "none"
-        if tta_on:  # the counts of the merged masks; pixels with 0 < votes < K
-            n_views = len(unet_hip.functional.tta_view_numbers(tta))
-            unet_hip.functional._tta_mode(tta_mode)
-            tcounts = torch.zeros(6, dtype=torch.int64, device=self.device)
-            tdis = torch.zeros(1, dtype=torch.int64, device=self.device)
-        src = " (TTA mask)" if tta_on else ""
-        curve_on = bool(getattr(cfg, "curve_metrics", False))
-        bins = int(getattr(cfg, "curve_bins", None) or 256)
-        criterion, opt_k = unet_hip.functional.parse_threshold(getattr(cfg, "threshold", None), bins)
-        opt_on = criterion is not None or opt_k is not None
-        if opt_on and tta_on:
-            raise ValueError(f"threshold={cfg.threshold!r} with tta={tta!r}: merging the views at a threshold "
-                             "other than 0.5 is not supported; use one of the two")
-        if curve_on or opt_on:
-            edges = unet_hip.curve_edges(bins).to(self.device)
-        if criterion is not None:  # the validation split decides the operating point
-            vs = self._curve_summary(self._curve_sweep(self.val_loader, edges, "Threshold sweep (val)"), edges)
-            opt_k = vs["best_global_k" if criterion == "val-dice" else "best_image_k"]
-        if opt_on:
-            ocounts = torch.zeros(6, dtype=torch.int64, device=self.device)
-        if curve_on:  # the histogram rows + ignored pixels, the Dice sums, the planes
-            cacc = self._curve_acc(bins)
         for batch in tqdm(self.test_loader, desc="Testing Model", leave=True):
             if batch is None:  # empty DataParallel shard: nothing to count on this rank
                 keep.append(None)
                 continue
             images, masks = batch
-            images = images.to(self.device).float()
-            masks = masks.to(self.device).float()
-            if tta_on:  # the first view is the identity: its logits are the plain forward's
-                merged = unet_hip.tta_predict(self.model, images, tta, tta_mode)
-                logits = merged["logits"][:images.size(0)]
-            else:
-                logits = self.model(images)
-            mask = torch.empty(logits.shape, dtype=torch.uint8, device=self.device)
-            self.rt.mask_counts(logits, masks, counts, mask)
-            raw = logits
-            if tta_on:
-                # the merged mask as +-1 logits, so that every kernel downstream reads the mask
-                # the merge formed (in "prob" mode the score is a probability, not a logit)
-                mask = merged["mask"]
-                logits = mask.float() * 2 - 1
-                self.rt.mask_counts(logits, masks, tcounts)
-                tdis += ((merged["votes"] > 0) & (merged["votes"] < n_views)).sum()
-            if curve_on:  # (no TTA with a threshold; under TTA `raw` is the first view's logits)
-                self._curve_add(cacc, raw, masks, edges)
-            if opt_on:  # the mask of operating point opt_k as +-1 logits for the same readout
-                om = unet_hip.functional.curve_predict(raw[:, :1], opt_k, edges)
-                self.rt.mask_counts(om.float() * 2 - 1, masks[:, :1].contiguous(), ocounts)
-            if surface:
-                ssums += self._surface_sums(logits, masks)
-            if post:
-                # the cleaned mask as +-1 logits: the existing readout and surface kernels count it
-                clean, _ = unet_hip.postprocess_mask(mask, **pp)
-                plog = clean[:, None].float() * 2 - 1
-                self.rt.mask_counts(plog, masks[:, :1].contiguous(), pcounts)
-                if surface:
-                    psums += self._surface_sums(plog, masks[:, :1].contiguous())
-            if lesion:
-                les = unet_hip.lesion_metrics(clean if post else mask, masks, pp["connectivity"])
-                lsums += torch.stack([les[k].sum() for k in unet_hip.functional.LESION_FIELDS])
-            if shape:
-                shape_rows.append(torch.cat([self._largest_row(clean if post else mask, pp["connectivity"], None),
-                                             self._largest_row(masks, pp["connectivity"], "targets")], 1))
+            rec = TB.Batch(sw, self.model, images.to(self.device).float(), masks.to(self.device).float())
+            for block in blocks:
+                block.add(rec)
             total += images.size(0)
-            keep.append((images.cpu(), masks.cpu(), mask.cpu()))
+            keep.append((rec.images.cpu(), rec.masks.cpu(), rec.mask.cpu()))
         if _distributed():
             nt = torch.tensor([total], dtype=torch.int64, device=self.device)
             dist.all_reduce(nt)
             total = int(nt.item())
-        m = global_metrics_from_counts(self._reduce_counts(counts).tolist())
-        msg = (f"Test Metrics  —  Total Images: {total}\n"
-               f"  TP={m['TP']}, FP={m['FP']}, FN={m['FN']}, TN={m['TN']}\n"
-               f"  ACC={m['ACC']:.4f}, Precision={m['Precision']:.4f}, "
-               f"Recall={m['Recall']:.4f}, F1={m['F1']:.4f}, IoU={m['IoU']:.4f}")
-        if self.rank0:
-            print(msg)
-        self.logger.info(msg)
-        if tta_on:
-            tm = global_metrics_from_counts(self._reduce_counts(tcounts).tolist())
-            if _distributed():
-                dist.all_reduce(tdis)
-            n_dis = int(tdis.item())  # the one transfer
-            n_pix = tm["TP"] + tm["FP"] + tm["FN"] + tm["TN"]
-            dis = n_dis / n_pix if n_pix else float("nan")
-            tmsg = (f"TTA ({tta}, {tta_mode})\n"
-                    f"  TP={tm['TP']}, FP={tm['FP']}, FN={tm['FN']}, TN={tm['TN']}\n"
-                    f"  ACC={tm['ACC']:.4f}, Precision={tm['Precision']:.4f}, "
-                    f"Recall={tm['Recall']:.4f}, F1={tm['F1']:.4f}, IoU={tm['IoU']:.4f}\n"
-                    f"  Disagreement={dis:.4f} ({n_dis} of {n_pix} pixels, {n_views} views)")
-            if self.rank0:
-                print(tmsg)
-            self.logger.info(tmsg)
-            m.update({"TTA_" + k: v for k, v in tm.items()})
-            m["TTA_Disagreement"] = dis
-        if surface:
-            if _distributed():
-                dist.all_reduce(ssums)
-            hd95, hd, assd, k, u = ssums.tolist()  # the one transfer
-            k, u = int(k), int(u)
-            hd95, hd, assd = ((v / k if k else float("nan")) for v in (hd95, hd, assd))
-            smsg = (f"Surface Metrics{src} — HD95={hd95:.4f}, HD={hd:.4f}, ASSD={assd:.4f} px "
-                    f"over {k} of {total} images ({u} undefined)")
-            if self.rank0:
-                print(smsg)
-            self.logger.info(smsg)
-            m.update(HD95=hd95, HD=hd, ASSD=assd, SurfaceDefined=k)
-        if post:
-            pm = global_metrics_from_counts(self._reduce_counts(pcounts).tolist())
-            pmsg = (f"Post-processed (largest={int(pp['keep_largest'])}, min_area={pp['min_area']}, "
-                    f"fill_holes={int(pp['fill_holes'])}, connectivity={pp['connectivity']}){src}\n"
-                    f"  TP={pm['TP']}, FP={pm['FP']}, FN={pm['FN']}, TN={pm['TN']}\n"
-                    f"  ACC={pm['ACC']:.4f}, Precision={pm['Precision']:.4f}, "
-                    f"Recall={pm['Recall']:.4f}, F1={pm['F1']:.4f}, IoU={pm['IoU']:.4f}")
-            m.update({"PP_" + k: v for k, v in pm.items()})
-            if surface:
-                if _distributed():
-                    dist.all_reduce(psums)
-                hd95, hd, assd, k, u = psums.tolist()
-                k, u = int(k), int(u)
-                hd95, hd, assd = ((v / k if k else float("nan")) for v in (hd95, hd, assd))
-                pmsg += (f"\n  HD95={hd95:.4f}, HD={hd:.4f}, ASSD={assd:.4f} px over {k} of {total} "
-                         f"images ({u} undefined)")
-                m.update(PP_HD95=hd95, PP_HD=hd, PP_ASSD=assd, PP_SurfaceDefined=k)
-            if self.rank0:
-                print(pmsg)
-            self.logger.info(pmsg)
-        if lesion:
-            if _distributed():
-                dist.all_reduce(lsums)
-            n_pred, n_gt, gt_hit, pred_hit = lsums.tolist()  # the one transfer
-            nan = float("nan")
-            rec = gt_hit / n_gt if n_gt else nan
-            prec = pred_hit / n_pred if n_pred else nan
-            fpc = (n_pred - pred_hit) / total if total else nan
-            lmsg = (f"Lesion Metrics ({('post-processed' if post else 'raw') + (' TTA' if tta_on else '')} "
-                    f"masks, connectivity "
-                    f"{pp['connectivity']}) — Recall={rec:.4f} ({gt_hit}/{n_gt}), Precision={prec:.4f} "
-                    f"({pred_hit}/{n_pred}), FP components/image={fpc:.4f}")
-            if self.rank0:
-                print(lmsg)
-            self.logger.info(lmsg)
-            m.update(LesionRecall=rec, LesionPrecision=prec, FPComponentsPerImage=fpc,
-                     PredComponents=n_pred, GTComponents=n_gt)
-        if curve_on:
-            cs = self._curve_summary(cacc, edges)  # the one transfer
-            cmsg = (f"Curve Metrics ({bins} bins) — AUROC={cs['auroc']:.4f}, AP={cs['ap']:.4f}\n"
-                    f"  Best global Dice={cs['best_global_dice']:.4f} at threshold {cs['best_global_threshold']:.4f} "
-                    f"(Dice at 0.5: {cs['dice_global_half']:.4f})\n"
-                    f"  Best mean per-image Dice={cs['best_image_dice']:.4f} at threshold "
-                    f"{cs['best_image_threshold']:.4f} (at 0.5: {cs['dice_image_half']:.4f}) over {cs['planes']} images\n"
-                    f"  Ignored pixels={cs['ignored']}")
-            if self.rank0:
-                print(cmsg)
-            self.logger.info(cmsg)
-            m.update(Curve_AUROC=cs["auroc"], Curve_AP=cs["ap"], Curve_BestDice=cs["best_global_dice"],
-                     Curve_BestDiceThreshold=cs["best_global_threshold"], Curve_Dice=cs["dice_global_half"],
-                     Curve_BestImageDice=cs["best_image_dice"],
-                     Curve_BestImageDiceThreshold=cs["best_image_threshold"],
-                     Curve_ImageDice=cs["dice_image_half"], Curve_Ignored=cs["ignored"], Curve_Bins=bins)
-        if opt_on:
-            om = global_metrics_from_counts(self._reduce_counts(ocounts).tolist())
-            how = f"chosen by {criterion}" if criterion else f"snapped from {float(cfg.threshold):g}"
-            omsg = (f"Operating point — threshold {opt_k / bins:.6f} (k={opt_k} of {bins}, {how})\n"
-                    f"  TP={om['TP']}, FP={om['FP']}, FN={om['FN']}, TN={om['TN']}\n"
-                    f"  ACC={om['ACC']:.4f}, Precision={om['Precision']:.4f}, "
-                    f"Recall={om['Recall']:.4f}, F1={om['F1']:.4f}, IoU={om['IoU']:.4f}")
-            if self.rank0:
-                print(omsg)
-            self.logger.info(omsg)
-            m.update({"OPT_" + k: v for k, v in om.items()})
-            m["OPT_Threshold"] = opt_k / bins
-        if shape:
-            rows = (torch.cat(shape_rows) if shape_rows else torch.zeros((0, 32), dtype=torch.int64)).cpu()  # the one transfer
-            sums = torch.from_numpy(unet_hip.functional.shape_agreement(rows[:, :16], rows[:, 16:]))
-            if _distributed():
-                sums = sums.to(self.device)
-                dist.all_reduce(sums)
-            sh = unet_hip.functional.shape_summary(sums.tolist())
-            shmsg = (f"SHAPE (largest component, {('post-processed' if post else 'raw') + (' TTA' if tta_on else '')} "
-                     f"masks, connectivity {pp['connectivity']}) — pairs={sh['n_pairs']} of {total} images\n"
-                     f"  Feret MAE={sh['feret_mae']:.4f} px, area rel. error={sh['area_rel_err']:.4f}, "
-                     f"centroid distance={sh['centroid_dist']:.4f} px\n"
-                     f"  taller-than-wide (pred/gt): both={sh['ttw'][0]}, pred only={sh['ttw'][1]}, "
-                     f"gt only={sh['ttw'][2]}, neither={sh['ttw'][3]}, kappa={sh['kappa']:.4f}")
-            if self.rank0:
-                print(shmsg)
-            self.logger.info(shmsg)
-            m.update(Shape_Pairs=sh["n_pairs"], Shape_FeretMAE=sh["feret_mae"], Shape_AreaRelErr=sh["area_rel_err"],
-                     Shape_CentroidDist=sh["centroid_dist"], Shape_TTW=sh["ttw"], Shape_TTWKappa=sh["kappa"])
+        m = {}
+        for block in blocks:
+            msg, entries = block.finish(total)
+            TB.report(msg, self.logger, self.rank0)
+            m.update(entries)
         if _distributed() and (self._can_plot() or save_overlays):
             # one set of PNGs over the whole test set, in the reference's sample order: batch
             # by batch, each batch's shards in rank order (DataParallel's gather order)
@@ -589,15 +405,6 @@ class Trainer:
         if save_overlays and self.rank0:
             self._save_overlays(keep)
         return m
-
-    @staticmethod
-    def _largest_row(x, connectivity, kind):
-        """int64 (N, 16): the morphometry row of every sample's largest component (the cc_key rule of
-        ``postprocess_mask``: largest area, then first in raster order; zeros for an empty mask), on the
-        device with no synchronisation -- the mask of that component alone has one label, so one table
-        row holds it."""
-        one, _ = unet_hip.postprocess_mask(x, keep_largest=True, connectivity=connectivity, kind=kind)
-        return unet_hip.lesion_morphometry(one, connectivity, max_rows=1)["table"][:, 0]
 
     def _save_overlays(self, keep):
         """One PNG per kept sample (images, targets, predicted mask as CPU batches), rendered on the
@@ -618,50 +425,6 @@ class Trainer:
                 Image.fromarray(rgb.cpu().numpy(), "RGB").save(
                     os.path.join(cfg.result_dir, f"test_overlay_{idx}.png"))
                 idx += 1
-
-    # ---- threshold sweep: device-side accumulators, read once ----
-    def _curve_acc(self, bins):
-        return dict(total=torch.zeros(2 * bins + 1, dtype=torch.int64, device=self.device),
-                    dice=torch.zeros(bins + 1, dtype=torch.float64, device=self.device), planes=0)
-
-    @staticmethod
-    def _curve_add(acc, logits, masks, edges):
-        """One histogram and one statistics call on the batch's channel-0 planes."""
-        ph, _ = unet_hip.curve_hist(logits[:, :1], masks[:, :1], edges, acc["total"])
-        unet_hip.curve_stats(ph, acc["dice"])
-        acc["planes"] += logits.shape[0]
-
-    def _curve_sweep(self, loader, edges, desc):
-        """The sweep over a loader in eval mode (the caller has synchronised the BN buffers)."""
-        acc = self._curve_acc(edges.numel() + 1)
-        for batch in tqdm(loader, desc=desc, leave=True):
-            if batch is None:  # empty DataParallel shard
-                continue
-            images, masks = batch
-            logits = self.model(images.to(self.device).float())
-            self._curve_add(acc, logits, masks.to(self.device).float(), edges)
-        return acc
-
-    def _curve_summary(self, acc, edges):
-        """All-reduce the accumulators, bring them back in one transfer, read the curves."""
-        ints = torch.cat([acc["total"], torch.tensor([acc["planes"]], dtype=torch.int64, device=self.device)])
-        if _distributed():
-            dist.all_reduce(ints)
-            dist.all_reduce(acc["dice"])
-        back = torch.cat([ints, acc["dice"].view(torch.int64)]).cpu()  # the one transfer
-        n = ints.numel()
-        return unet_hip.curve_summary(back[:n - 1].tolist(), back[n:].view(torch.float64).tolist(),
-                                      int(back[n - 1]), edges)
-
-    @staticmethod
-    def _surface_sums(logits, masks):
-        """float64[5] on the device: the batch's sums of the per-sample hd95, hd and assd over its
-        defined samples, then how many are defined and how many are not (P or G empty)."""
-        s = unet_hip.surface_metrics(logits, masks)
-        ok = s["defined"] != 0
-        zero = torch.zeros_like(s["hd"])
-        parts = [torch.where(ok, s[k], zero).sum() for k in ("hd95", "hd", "assd")]
-        return torch.stack(parts + [ok.sum().double(), (~ok).sum().double()])
 
     @staticmethod
     def _can_plot():
